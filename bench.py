@@ -10,13 +10,20 @@ collective ("weak" scaling: every rank evaluates its own 100 Mb shard).
 One "step" = one tehmm_eval_batch(VITERBI | POSTERIOR) over the rank's whole batch of intervals,
 observations already resident in HBM, results left in HBM (paths int64 + posteriors f64).  Every timed
 step is a FIRST evaluation of its batch as far as derived data go (tehmm_batch_reset_cache drops the
-table-row index records of the fused passes): teHmmEval evaluates a batch once.  After the timing two
-intervals of the workload (the shortest and one of >= 1 Mb) are compared with the CPU oracle:
-`"verified": true` means paths and Viterbi scores bit-exact, posteriors and log-likelihood within 1e-6.
+table-row index records of the fused passes): teHmmEval evaluates a batch once.
 `--scaling strong`: ONE config-3 interval list (the 9 alyrata scaffolds, 196 Mb, cut at synthetic mask
 gaps) LPT-sharded over the ranks (tehmm_amd.dist.lpt_shard) instead of 100 Mb per rank.
 `--mode estep` times BASELINE config 4 instead (Baum-Welch iterations: fused E-step per rank, ONE
 all-reduce of the packed statistics over RCCL, device M-step).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds, after the timing, what
+else the benchmark measures and checks: two intervals of the workload (the shortest and one of >= 1 Mb)
+compared with the CPU oracle (`"verified": true` means paths and Viterbi scores bit-exact, posteriors and
+log-likelihood within 1e-6; `--mode estep`: four chunks of statistics), the other BASELINE shapes
+(`extra`), the CPU baseline, and on several ranks the gather of the per-interval scores; `--no-verify`,
+`--no-extra` and `--no-cpu-baseline` drop parts of it.
+`--dump-outputs DIR` writes what the last timed step computed, as float64 .npy files (see dump_eval /
+em_iterations); the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -44,16 +51,23 @@ def parse_args():
     ap.add_argument("--mode", choices=("eval", "estep"), default="eval")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --mb per GPU; strong: one 196 Mb whole-genome interval list sharded over the GPUs")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of two bench intervals")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timing also run the oracle checks, the extra measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the oracle check of two bench intervals")
     ap.add_argument("--mb", type=float, default=None, help="Mb of genome per GPU (eval: 100, estep: 200)")
     ap.add_argument("--min-kb", type=int, default=200, help="shortest interval (kb)")
     ap.add_argument("--max-kb", type=int, default=2000, help="longest interval (kb)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the untimed extra measurements (other BASELINE configs, model variants, PCIe)")
+                    help="with --full: skip the untimed extra measurements (other BASELINE configs, model variants, PCIe)")
     ap.add_argument("--cpu-sample-kb", type=int, default=250,
                     help="positions per CPU-baseline interval (kb); 4 intervals per thread")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -178,6 +192,23 @@ def verify_intervals(model, hb, obs, offs, res, n_threads=2):
             "posterior_max_rel_err": worst, "verify_s": time.perf_counter() - t0}
 
 
+def dump_eval(dirname, hb, res, n_states, n_blocks=64, block=1024, seed=2024):
+    """--dump-outputs of the eval step: what tehmm_eval_batch hands its caller, as float64.  The per-interval Viterbi
+    and forward log-likelihoods in full; the Viterbi path and the posterior rows (all of them would be 8 + 8 N bytes a
+    position, GBs) at a fixed, seeded sample of n_blocks aligned blocks of `block` positions, ~19 MB at N = 35."""
+    os.makedirs(dirname, exist_ok=True)
+    total = hb.total
+    block = min(block, total)
+    n_grid = total // block
+    starts = np.sort(np.random.default_rng(seed).choice(n_grid, size=min(n_blocks, n_grid), replace=False)) * block
+    out = {"viterbi_logprob": res["viterbi_logprob"], "forward_logprob": res["forward_logprob"],
+           "sample_positions": np.concatenate([np.arange(a, a + block) for a in starts]),
+           "viterbi_path": np.concatenate([hb.paths(a, a + block) for a in starts]),
+           "posteriors": np.concatenate([hb.posteriors(n_states, a, a + block) for a in starts])}
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def cpu_baseline_estep(n_seq=4, per_seq=100_000):
     """The oracle's E-step (forward, backward, xi log-sum, emission statistics per sequence: basehmm.py:504-523 as
     restated in oracle/) on a bounded sample of the config-4 workload, one core (the reference is single-threaded)."""
@@ -287,6 +318,9 @@ def run_eval(args, rank, world, local_rank):
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_eval(args.dump_outputs, hb, res, model.n_states)
+    if use_dist and args.full:
         # the "trivial gather" of the per-interval scores (north_star): exercised once, outside the timing
         from tehmm_amd import dist as tdist
         if strong:
@@ -298,7 +332,7 @@ def run_eval(args, rank, world, local_rank):
             first = sum(len(r) for r in rank_lens[:rank])
             tdist.gather_interval_scalars(np.arange(first, first + len(lens)), res["viterbi_logprob"], len(flat))
     verdict = None
-    if rank == 0 and not args.no_verify and res is not None:
+    if rank == 0 and args.full and not args.no_verify:
         verdict = verify_intervals(model, hb, obs, offs, res)
 
     if rank == 0:
@@ -370,9 +404,9 @@ def run_eval(args, rank, world, local_rank):
         }
         if verdict is not None:
             out.update(verdict)
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             out["extra"] = extras(args, model, hm, hb, obs, offs, lens, device, torch, mk_model)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             nthr = max(1, min(16, os.cpu_count() or 1))
             cb = cpu_baseline(model, nthr, args.cpu_sample_kb * 1000, 4 * nthr)
             cb["one_core"] = cpu_baseline(model, 1, args.cpu_sample_kb * 1000, 2)
@@ -681,9 +715,11 @@ def estep_other_routes(which, torch, device, verify=True):
     return out
 
 
-def em_iterations(mb, n_iter, device, torch, dist, verify=False):
+def em_iterations(mb, n_iter, device, torch, dist, verify=False, warmup=1, dump_dir=None):
     """Baum-Welch iterations on the config-4 shape: per iteration one fused E-step over the rank's 100 kb
-    chunks (statistics left on the device), ONE all-reduce of the flat statistics buffer, device M-step."""
+    chunks (statistics left on the device), ONE all-reduce of the flat statistics buffer, device M-step.
+    dump_dir: --dump-outputs of the last iteration (float64): the statistics the M-step consumed and the model it
+    made (log transition matrix, log start probabilities, log emission tables)."""
     from tehmm_amd import synth
     from tehmm_amd.engine import DeviceStats, HipBatch, HipModel
     m4 = synth.make_model(N_STATES, synth.CONFIG4_SYMBOLS, synth.CONFIG4_GAUSSIAN, seed=0)
@@ -706,7 +742,8 @@ def em_iterations(mb, n_iter, device, torch, dist, verify=False):
             dist.all_reduce(st.tensor, op=dist.ReduceOp.SUM)
         lps.append(st.head()[0])
         hm4.mstep(st, False, True, True, 1.0, 1.0, 0.0, None)
-    one_iteration()                         # warm-up (workspace allocation)
+    for _ in range(warmup):
+        one_iteration()                     # warm-up (workspace allocation)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -719,6 +756,11 @@ def em_iterations(mb, n_iter, device, torch, dist, verify=False):
     d = (time.perf_counter() - t1) / n_iter
     n = int(o4[-1])
     stage_ms = {k: v for k, v in hb4.timing().items() if not k.startswith("count:")}
+    if dump_dir:
+        os.makedirs(dump_dir, exist_ok=True)
+        lt, pi, lp = hm4.get_params(start.log_probs)
+        for name, a in (("statistics", st.to_host()), ("log_transmat", lt), ("log_startprob", pi), ("log_probs", lp)):
+            np.save(os.path.join(dump_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
     hb4.close()
     st.close()
     hm4.close()
@@ -750,12 +792,14 @@ def run_estep(args, rank, world, local_rank):
     if use_dist:
         init_dist(dist, device)
     mb = 200.0 if args.mb is None else args.mb
-    r = em_iterations(mb, args.steps, device, torch, dist if use_dist else None, verify=(rank == 0 and not args.no_verify))
+    r = em_iterations(mb, args.steps, device, torch, dist if use_dist else None,
+                      verify=(rank == 0 and args.full and not args.no_verify), warmup=args.warmup,
+                      dump_dir=args.dump_outputs if rank == 0 else None)
     if rank == 0:
         d = r["ms_per_iteration"] * 1e-3
         value = r["positions"] * world / d
         out = {"metric": "genome positions/sec (Baum-Welch EM iteration), 35 states x 12 tracks",
-               "value": value, "unit": "positions/s", "n_gpus": world, "steps": args.steps, "warmup": 1,
+               "value": value, "unit": "positions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": d * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                "dtype": "f64", "data": "synthetic",
                "config": {"workload": "teHmmTrain E-step + all-reduce + M-step, 35 states, 12 tracks (10 multinomial "
@@ -782,7 +826,7 @@ def run_estep(args, rank, world, local_rank):
         for k in ("verified", "verified_chunks", "statistics_max_rel_err", "verify_s"):
             if k in r:
                 out[k] = r[k]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_estep()
         print(json.dumps(out))
     if use_dist:

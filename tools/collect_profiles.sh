@@ -33,8 +33,8 @@ if has traffic; then
 fi
 if has estep; then
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_prof_estep" -o "${tag}_estep" -- \
-    $B --mode estep --mb 50 --steps 3 --warmup 1 > "$out/${tag}_estep_under_rocprof.json" 2> "$out/${tag}_prof_estep.err" || exit 5
-  timeout -k 10 400 $B --mode estep --mb 50 --steps 3 --warmup 1 > "$out/${tag}_bench_estep.json" 2> "$out/${tag}_bench_estep.err" || exit 6
+    $B --mode estep --mb 50 --steps 3 --warmup 1 --full > "$out/${tag}_estep_under_rocprof.json" 2> "$out/${tag}_prof_estep.err" || exit 5
+  timeout -k 10 400 $B --mode estep --mb 50 --steps 3 --warmup 1 --full > "$out/${tag}_bench_estep.json" 2> "$out/${tag}_bench_estep.err" || exit 6
   echo "estep done"
 fi
 if has esteptraffic; then
@@ -62,7 +62,7 @@ if has wide; then
   echo "wide done"
 fi
 if has strong; then
-  timeout -k 10 400 $B --scaling strong --no-extra > "$out/${tag}_bench_strong_1gpu.json" 2> "$out/${tag}_bench_strong.err" || exit 7
+  timeout -k 10 400 $B --scaling strong --full --no-extra > "$out/${tag}_bench_strong_1gpu.json" 2> "$out/${tag}_bench_strong.err" || exit 7
   echo "strong done"
 fi
 if has stage; then
