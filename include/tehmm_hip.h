@@ -33,11 +33,14 @@ extern "C" {
 #define TEHMM_ERR_UNSUPPORTED (-3) /* shape outside what the kernels support (see tehmm_max_states) */
 
 /* ---- library / device ---------------------------------------------------------------------- */
-int tehmm_abi_version(void);                 /* bumps when a signature changes or is added (3) */
+int tehmm_abi_version(void);                 /* bumps when a signature changes or is added (4) */
 const char *tehmm_last_error(void);          /* thread-local message of the last failing call */
 int tehmm_device_count(int *count);          /* hipGetDeviceCount */
 int tehmm_set_device(int device);            /* hipSetDevice; one process per GPU calls this once */
-int tehmm_max_states(void);                  /* largest N the fused kernels accept (128) */
+int tehmm_max_states(void);                  /* largest N of the fused / chunk-parallel paths and the device
+                                                 E-step and M-step (128) */
+int tehmm_max_states_any(void);              /* largest N any entry point accepts (1024): above 128 states a model
+                                                 evaluates through the sequential kernels of tehmm_large.hip.h */
 
 /* ---- array-level entry points: 1:1 replacements of the Cython module functions --------------
  * Caller owns every buffer (host memory); results are written in place exactly where the Cython
@@ -107,6 +110,9 @@ typedef struct tehmm_batch tehmm_batch_t;
  * and emissionModel.logProbs [K][N][S] + normalizeFac (emission.py:44,58-60).
  * symbolsPerTrack (may be NULL) = emissionModel.numSymbolsPerTrack: lets the library pack the
  * table raggedly (symbols 0..symbolsPerTrack[k] of track k); with NULL all S columns are kept. */
+/* N up to 1024 (K <= 128, S <= 256; larger: TEHMM_ERR_UNSUPPORTED before any device call).  Above 128 states the
+ * handle keeps only the tables of the sequential large-state kernels: tehmm_eval_batch, the result calls and
+ * tehmm_model_get_params take it, while the batch E-step, M-step and statistics calls return TEHMM_ERR_UNSUPPORTED. */
 int tehmm_model_create(int N, int K, int S, const double *log_transmat, const double *log_startprob,
                        const double *logProbs, double normalize, const int32_t *symbolsPerTrack,
                        tehmm_model_t **out);

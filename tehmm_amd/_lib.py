@@ -26,6 +26,7 @@ SIGNATURES = {
     "tehmm_device_count": (c_int, [ctypes.POINTER(c_int)]),
     "tehmm_set_device": (c_int, [c_int]),
     "tehmm_max_states": (c_int, []),
+    "tehmm_max_states_any": (c_int, []),
     "tehmm_emission_u8": (c_int, [c_i64, c_int, c_int, c_int, vp, f64p, c_dbl, f64p, f64p]),
     "tehmm_emission_u16": (c_int, [c_i64, c_int, c_int, c_int, vp, f64p, c_dbl, f64p, f64p]),
     "tehmm_emission_i32": (c_int, [c_i64, c_int, c_int, c_int, vp, f64p, c_dbl, f64p, f64p]),

@@ -70,6 +70,7 @@ int tehmm_mask_table_u8(int64_t T, int K, const uint8_t *data, int KM, const uin
 // ---- device-resident Baum-Welch: statistics buffers and the M-step --------------------------------
 int tehmm_stats_alloc(const tehmm_model_t *m, double **dev_stats) {
   if (!m || !dev_stats) return fail(TEHMM_ERR_ARG, "tehmm_stats_alloc: bad argument");
+  if (m->large) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_stats_alloc: no device-resident statistics for N > 128");
   *dev_stats = nullptr;
   HIPCHK(hipMalloc((void **)dev_stats, (size_t)stats_size(m->NP, m->R) * sizeof(double)));
   HIPCHK(hipMemset(*dev_stats, 0, (size_t)stats_size(m->NP, m->R) * sizeof(double)));
@@ -77,6 +78,7 @@ int tehmm_stats_alloc(const tehmm_model_t *m, double **dev_stats) {
 }
 int tehmm_stats_zero(const tehmm_model_t *m, double *dev_stats) {
   if (!m || !dev_stats) return fail(TEHMM_ERR_ARG, "tehmm_stats_zero: bad argument");
+  if (m->large) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_stats_zero: no device-resident statistics for N > 128");
   HIPCHK(hipMemset(dev_stats, 0, (size_t)stats_size(m->NP, m->R) * sizeof(double)));
   return TEHMM_OK;
 }
@@ -95,6 +97,7 @@ int tehmm_stats_head(const double *dev_stats, double *logprob_sum, double *nobs)
 
 int tehmm_stats_copy(const tehmm_model_t *m, double *dev_stats, double *host_buf, int to_device) {
   if (!m || !dev_stats || !host_buf) return fail(TEHMM_ERR_ARG, "tehmm_stats_copy: bad argument");
+  if (m->large) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_stats_copy: no device-resident statistics for N > 128");
   const size_t bytes = (size_t)stats_size(m->NP, m->R) * sizeof(double);
   if (to_device) HIPCHK(hipMemcpy(dev_stats, host_buf, bytes, hipMemcpyHostToDevice));
   else HIPCHK(hipMemcpy(host_buf, dev_stats, bytes, hipMemcpyDeviceToHost));
@@ -115,7 +118,7 @@ int tehmm_model_mstep(tehmm_model_t *m, const double *dev_stats, int update_star
                       double *gauss_params) {
   if (!m || !dev_stats || n_gauss < 0 || (n_gauss > 0 && (!gauss_tracks || !gauss_values)))
     return fail(TEHMM_ERR_ARG, "tehmm_model_mstep: bad argument");
-  if (m->N > 128) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_mstep: N > 128");
+  if (m->N > 128) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_mstep: N > 128 (no device-resident M-step)");
   for (int g = 0; g < n_gauss; ++g)
     if (gauss_tracks[g] < 0 || gauss_tracks[g] >= m->K)
       return fail(TEHMM_ERR_ARG, "tehmm_model_mstep: gaussian track index out of range");

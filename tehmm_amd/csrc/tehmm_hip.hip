@@ -11,6 +11,7 @@
 #include "tehmm_estep.hip.h"
 #include "tehmm_wide_estep.hip.h"
 #include "tehmm_wide.hip.h"
+#include "tehmm_large.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -284,6 +285,7 @@ struct tehmm_model {
   DBuf<double> ptab, ptab_lds;
   DBuf<int> d_rowinfo;         // rowbase[K] | rowcnt[K] | ldsbase[K] on the device
   int KSP = 0;
+  bool large = false;          // 129 <= N <= 1024: only lt, A, AT, pi and tab exist (tehmm_large.hip.h, eval_large)
   uint64_t uid = 0;            // unique per model handle (workspaces derived from the table layout are keyed on it)
   uint64_t version = 0;        // bumped by every M-step (what depends on the parameter VALUES is keyed on it too)
   bool ptab_log = false;       // log-domain rows (normalizeFac != 1): the product form does not apply
@@ -457,9 +459,10 @@ struct tehmm_batch {
 
 // All tehmm_* functions below are declared extern "C" in include/tehmm_hip.h.
 
-int tehmm_abi_version(void) { return 3; }
+int tehmm_abi_version(void) { return 4; }
 const char *tehmm_last_error(void) { return g_err.c_str(); }
 int tehmm_max_states(void) { return kMaxStates; }
+int tehmm_max_states_any(void) { return TEHMM_LARGE_MAX; }
 
 int tehmm_device_count(int *count) {
   if (!count) return fail(TEHMM_ERR_ARG, "count is NULL");
@@ -669,6 +672,70 @@ static int build_ptab(tehmm_model *m) {
   return TEHMM_OK;
 }
 
+// 129 <= N <= 1024 (tehmm_large.hip.h): only what the large kernels read -- lt, A, AT ([NP][NP], NP = N rounded up
+// to 64, padding states with -inf / 0), pi and the emission rows tab [R + 1][NP] with their row bases.  No quantised,
+// group-major or LDS-staged copies: the fused, chunk-parallel and E-step paths refuse such a model.
+static int model_create_large(int N, int K, int S, const double *lt, const double *pi, const double *logProbs,
+                              double normalize, const int32_t *symbolsPerTrack, tehmm_model_t **out) {
+  tehmm_model *m = new tehmm_model();
+  {
+    static std::atomic<uint64_t> next_uid{1u << 30};      // (own sequence: no workspace is keyed on a large model)
+    m->uid = next_uid.fetch_add(1);
+  }
+  m->N = N;
+  m->K = K;
+  m->S = S;
+  m->NP = large_geom(N).NP;
+  m->normalize = normalize;
+  m->large = true;
+  const int NP = m->NP;
+  std::vector<double> hlt((size_t)NP * NP, -INFINITY), hA((size_t)NP * NP, 0.0), hAT((size_t)NP * NP, 0.0),
+      hpi(NP, -INFINITY);
+  for (int i = 0; i < N; ++i) {
+    hpi[i] = pi[i];
+    for (int j = 0; j < N; ++j) {
+      const double l = lt[(size_t)i * N + j];
+      hlt[(size_t)i * NP + j] = l;
+      const double a = std::exp(l);
+      hA[(size_t)i * NP + j] = a;
+      hAT[(size_t)j * NP + i] = a;
+    }
+  }
+  m->h_lt.assign(lt, lt + (size_t)N * N);
+  int R = 0;
+  for (int k = 0; k < K; ++k) {
+    int cnt = S;
+    if (symbolsPerTrack) {
+      cnt = symbolsPerTrack[k] + 1;
+      if (cnt < 1) cnt = 1;
+      if (cnt > S) cnt = S;
+    }
+    m->rowbase[k] = R;
+    m->rowcnt[k] = cnt;
+    m->ldsbase[k] = -1;
+    R += cnt;
+  }
+  m->R = R;
+  m->lds_rows = 0;
+  m->lds_zero = 0;
+  std::vector<double> htab((size_t)(R + 1) * NP, 0.0);      // row R: the zero padding (EmisTab::zero_row)
+  for (int k = 0; k < K; ++k)
+    for (int s = 0; s < m->rowcnt[k]; ++s)
+      for (int j = 0; j < N; ++j)
+        htab[(size_t)(m->rowbase[k] + s) * NP + j] = logProbs[((size_t)k * N + j) * S + s];
+  hipError_t e = m->lt.upload(hlt.data(), hlt.size());
+  if (e == hipSuccess) e = m->A.upload(hA.data(), hA.size());
+  if (e == hipSuccess) e = m->AT.upload(hAT.data(), hAT.size());
+  if (e == hipSuccess) e = m->pi.upload(hpi.data(), hpi.size());
+  if (e == hipSuccess) e = m->tab.upload(htab.data(), htab.size());
+  if (e != hipSuccess) {
+    delete m;
+    return fail(TEHMM_ERR_HIP, std::string("tehmm_model_create: ") + hipGetErrorString(e));
+  }
+  *out = m;
+  return TEHMM_OK;
+}
+
 int tehmm_model_create(int N, int K, int S, const double *lt, const double *pi,
                        const double *logProbs, double normalize, const int32_t *symbolsPerTrack,
                        tehmm_model_t **out) {
@@ -676,8 +743,9 @@ int tehmm_model_create(int N, int K, int S, const double *lt, const double *pi,
   *out = nullptr;
   if (N <= 0 || K <= 0 || S <= 0 || !lt || !pi || !logProbs)
     return fail(TEHMM_ERR_ARG, "tehmm_model_create: bad argument");
-  if (N > kMaxStates || K > TEHMM_MAX_TRACKS || S > 256)
-    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_create: N > 128, K > 128 or S > 256");
+  if (N > TEHMM_LARGE_MAX || K > TEHMM_MAX_TRACKS || S > 256)
+    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_create: N > 1024, K > 128 or S > 256");
+  if (N > kMaxStates) return model_create_large(N, K, S, lt, pi, logProbs, normalize, symbolsPerTrack, out);
   tehmm_model *m = new tehmm_model();
   {
     static std::atomic<uint64_t> next_uid{1};
@@ -2503,6 +2571,161 @@ static int fb_warmup(tehmm_batch *b, const tehmm_model *m, int LS, const Interva
   return TEHMM_OK;
 }
 
+// ---- 129 <= N <= 1024: sequential kernels of tehmm_large.hip.h ----------------------------------------------------
+// Traceback of the large Viterbi kernels: the chunk-parallel compose / scan / fill of the N <= 128 paths, on byte
+// pointers up to 256 states and 16-bit ones above (PtrT), the scans reading their chunk maps from global memory
+// (DIRECT: the rows are too wide to stage).  G must be zero-filled once (the scans also walk the padding states).
+template <typename PtrT>
+static int traceback_large(const IntervalTab &iv, int n, const int64_t *h_chunk0, int n_chunks, const int *d_chunk_iv,
+                           const int64_t *d_chunk0, int N, int NP, const uint8_t *tb, uint8_t *G, uint8_t *bstate,
+                           DBuf<uint8_t> &Gg, DBuf<uint8_t> &tstate, const int *last_state, int64_t *paths,
+                           hipStream_t st) {
+  constexpr int MS = sizeof(PtrT) == 1 ? 4 : 16;          // states per lane of the compose walk (N <= 256 / 1024)
+  const int stage = tb_stage_bytes(NP * (int)sizeof(PtrT));
+  allow_lds(k_tb_compose<PtrT, MS>, 4 * TEHMM_TB_STAGE);
+  allow_lds(k_tb_fill<PtrT>, 4 * TEHMM_TB_STAGE);
+  if (n_chunks > 0)
+    hipLaunchKernelGGL((k_tb_compose<PtrT, MS>), dim3((n_chunks + 3) / 4), dim3(256), 4 * stage, st, iv, d_chunk_iv,
+                       d_chunk0, n_chunks, N, NP, NP, (const PtrT *)tb, (PtrT *)G);
+  int64_t maxc = 0;
+  for (int i = 0; i < n; ++i) maxc = std::max<int64_t>(maxc, h_chunk0[i + 1] - h_chunk0[i]);
+  const int maxt = (int)((maxc + 63) / 64);
+  if (maxt > 8 && maxt <= 65535) {
+    const size_t ntile = (size_t)n_chunks / 64 + (size_t)n + 2;
+    HIPCHK(Gg.ensure(ntile * NP * sizeof(PtrT)));
+    HIPCHK(tstate.ensure(ntile * sizeof(PtrT)));
+    hipLaunchKernelGGL((k_tb_group<PtrT, true>), dim3(n, maxt), dim3(64), 0, st, iv, d_chunk0, NP, (const PtrT *)G,
+                       (PtrT *)Gg.p);
+    hipLaunchKernelGGL((k_tb_scan_top<PtrT, true>), dim3(n), dim3(64), 0, st, iv, d_chunk0, NP, (const PtrT *)Gg.p,
+                       last_state, (PtrT *)tstate.p, paths);
+    hipLaunchKernelGGL((k_tb_scan_tiles<PtrT, true>), dim3(n, maxt), dim3(64), 0, st, iv, d_chunk0, NP,
+                       (const PtrT *)G, (const PtrT *)tstate.p, (PtrT *)bstate);
+  } else {
+    hipLaunchKernelGGL((k_tb_scan<PtrT, true>), dim3(std::max(1, n)), dim3(64), 0, st, iv, d_chunk0, NP,
+                       (const PtrT *)G, last_state, (PtrT *)bstate, paths);
+  }
+  if (n_chunks > 0)
+    hipLaunchKernelGGL((k_tb_fill<PtrT>), dim3((n_chunks + 3) / 4), dim3(256), 4 * stage, st, iv, n_chunks, d_chunk_iv,
+                       d_chunk0, NP, (const PtrT *)tb, (const PtrT *)bstate, paths);
+  HIPCHK(hipGetLastError());
+  return TEHMM_OK;
+}
+
+template <typename PtrT>
+static void launch_vit_large(const IntervalTab &iv, const EmisTab &em, const LargeGeom &lg, int n_blocks, bool ratio,
+                             bool frame_in, const double *lt, const double *pi, const double *tratios,
+                             const double *frame, uint8_t *tb, int *last_state, double *logprob, hipStream_t st) {
+  const size_t lds = large_lds_bytes(lg);
+#define VIT_LARGE(R_, F_)                                                                                              \
+  do {                                                                                                                 \
+    allow_lds(k_vit_large<R_, F_, PtrT>, lds);                                                                         \
+    hipLaunchKernelGGL((k_vit_large<R_, F_, PtrT>), dim3(n_blocks), dim3(TEHMM_LARGE_BLOCK), lds, st, iv, em, lg, lt,  \
+                       pi, tratios, frame, (PtrT *)tb, last_state, logprob);                                           \
+  } while (0)
+  if (frame_in) {
+    if (ratio) VIT_LARGE(true, true); else VIT_LARGE(false, true);
+  } else {
+    if (ratio) VIT_LARGE(true, false); else VIT_LARGE(false, false);
+  }
+#undef VIT_LARGE
+}
+
+// tehmm_eval_batch on a large model: decode (Viterbi with the batch's segment ratios when asked, Q11) and / or
+// score_samples (forward / backward, never ratios, Q12), one workgroup per interval on each of the two streams.
+static int eval_large(tehmm_model *m, tehmm_batch *b, int flags, double *viterbi_logprob, double *forward_logprob) {
+  const LargeGeom lg = large_geom(m->N);
+  const bool vit = flags & TEHMM_EVAL_VITERBI, postr = flags & TEHMM_EVAL_POSTERIOR;
+  const bool ratio = (flags & TEHMM_EVAL_USE_RATIOS) && b->has_ratios;
+  const bool wide_ptr = m->N > 256;                         // a from-index no longer fits a byte
+  const size_t pb = wide_ptr ? 2 : 1;
+  if (b->N != m->N) {
+    b->paths.release();
+    b->post.release();
+    b->tb.release();
+    b->G.release();
+    b->beta.release();
+    b->N = m->N;
+    b->NP = m->NP;
+    b->TBW = m->NP;
+  }
+  if (vit && !b->paths.p) {
+    HIPCHK(b->paths.alloc((size_t)b->total + 1));
+    HIPCHK(b->tb.alloc((size_t)(b->total_pad + 1) * b->TBW * pb));
+    HIPCHK(b->G.alloc((size_t)(b->n_chunks + 1) * b->NP * pb));
+    HIPCHK(hipMemsetAsync(b->G.p, 0, (size_t)(b->n_chunks + 1) * b->NP * pb, b->sV));
+    HIPCHK(b->bstate.alloc((size_t)(b->n_chunks + 1) * pb));
+    HIPCHK(b->last_state.alloc((size_t)b->n + 1));
+    HIPCHK(b->vit_lp.alloc((size_t)b->n + 1));
+  }
+  if (postr && !b->post.p) {
+    HIPCHK(b->post.alloc((size_t)b->total * m->N + 1));
+    HIPCHK(b->fwd_lp.alloc((size_t)b->n + 1));
+    HIPCHK(b->first_good.alloc((size_t)b->n + 1));
+    HIPCHK(b->dead.alloc((size_t)b->n + 1));
+  }
+  IntervalTab iv;
+  EmisTab em;
+  fill_tabs(m, b, iv, em, false);   // decode / score_samples never apply ratios to emissions
+  const size_t lds = large_lds_bytes(lg);
+  if (postr) {
+    hipStream_t st = b->sP;
+    (void)hipEventRecord(b->ev[5], st);
+    allow_lds(k_fwd_large, lds);
+    allow_lds(k_bwd_large, lds);
+    hipLaunchKernelGGL(k_fwd_large, dim3(b->n), dim3(TEHMM_LARGE_BLOCK), lds, st, iv, em, lg, (const double *)m->A.p,
+                       (const double *)m->pi.p, b->post.p, b->fwd_lp.p, b->first_good.p);
+    (void)hipEventRecord(b->ev[6], st);
+    hipLaunchKernelGGL(k_bwd_large, dim3(b->n), dim3(TEHMM_LARGE_BLOCK), lds, st, iv, em, lg, (const double *)m->AT.p,
+                       b->post.p, (const int64_t *)b->first_good.p);
+    (void)hipEventRecord(b->ev[7], st);
+  }
+  if (vit) {
+    hipStream_t st = b->sV;
+    (void)hipEventRecord(b->ev[0], st);
+    if (wide_ptr)
+      launch_vit_large<uint16_t>(iv, em, lg, b->n, ratio, false, m->lt.p, m->pi.p, ratio ? b->ratios.p : nullptr,
+                                 nullptr, b->tb.p, b->last_state.p, b->vit_lp.p, st);
+    else
+      launch_vit_large<uint8_t>(iv, em, lg, b->n, ratio, false, m->lt.p, m->pi.p, ratio ? b->ratios.p : nullptr,
+                                nullptr, b->tb.p, b->last_state.p, b->vit_lp.p, st);
+    (void)hipEventRecord(b->ev[1], st);
+    const int rc = wide_ptr ? traceback_large<uint16_t>(iv, b->n, b->h_chunk0.data(), b->n_chunks, b->d_chunk_iv.p,
+                                                        b->d_chunk0.p, m->N, m->NP, b->tb.p, b->G.p, b->bstate.p, b->Gg,
+                                                        b->tstate, b->last_state.p, b->paths.p, st)
+                            : traceback_large<uint8_t>(iv, b->n, b->h_chunk0.data(), b->n_chunks, b->d_chunk_iv.p,
+                                                       b->d_chunk0.p, m->N, m->NP, b->tb.p, b->G.p, b->bstate.p, b->Gg,
+                                                       b->tstate, b->last_state.p, b->paths.p, st);
+    if (rc) return rc;
+    (void)hipEventRecord(b->ev[2], st);
+    b->tnames.push_back("k_vit_large");
+    b->tpairs.push_back({0, 1});
+    b->tnames.push_back("traceback");
+    b->tpairs.push_back({1, 2});
+  }
+  if (postr) {
+    b->tnames.push_back("k_fwd_large");
+    b->tpairs.push_back({5, 6});
+    b->tnames.push_back("k_bwd_large");
+    b->tpairs.push_back({6, 7});
+  }
+  HIPCHK(hipGetLastError());
+  if (vit) HIPCHK(hipStreamSynchronize(b->sV));
+  if (postr) HIPCHK(hipStreamSynchronize(b->sP));
+  for (auto &pr : b->tpairs) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, b->ev[pr.first], b->ev[pr.second]);
+    b->tms.push_back((double)ms);
+  }
+  if (vit && viterbi_logprob)
+    HIPCHK(hipMemcpy(viterbi_logprob, b->vit_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
+  if (postr) {
+    b->h_fwd_lp.resize((size_t)b->n);
+    HIPCHK(hipMemcpy(b->h_fwd_lp.data(), b->fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
+    if (forward_logprob) std::memcpy(forward_logprob, b->h_fwd_lp.data(), (size_t)b->n * sizeof(double));
+  }
+  return TEHMM_OK;
+}
+
 int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *viterbi_logprob,
                      double *forward_logprob) {
   if (!m || !b) return fail(TEHMM_ERR_ARG, "tehmm_eval_batch: NULL handle");
@@ -2513,6 +2736,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   b->tpairs.clear();
   b->tms.clear();
   if (b->n == 0 || b->total == 0) return TEHMM_OK;
+  if (m->large) return eval_large(m, b, flags, viterbi_logprob, forward_logprob);
 #ifdef TEHMM_DEV_NT
   if (m->N < 64 && m->NP != TEHMM_DEV_NT)
     return fail(TEHMM_ERR_UNSUPPORTED, "development build: fused kernels exist for one padded state count only");
@@ -3038,10 +3262,10 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
       }
     }
     (void)hipEventRecord(b->ev[eV + 1], st);
-    allow_lds(k_tb_compose, 4 * TEHMM_TB_STAGE);
-    allow_lds(k_tb_fill, 4 * TEHMM_TB_STAGE);
+    allow_lds(k_tb_compose<uint8_t>, 4 * TEHMM_TB_STAGE);
+    allow_lds(k_tb_fill<uint8_t>, 4 * TEHMM_TB_STAGE);
     if (b->n_chunks > 0)
-      hipLaunchKernelGGL(k_tb_compose, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv, b->d_chunk_iv.p,
+      hipLaunchKernelGGL(k_tb_compose<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv, b->d_chunk_iv.p,
                          b->d_chunk0.p, b->n_chunks, m->N, m->NP, b->TBW, b->tb.p, b->G.p);
     {
       // long intervals: two-level scan (tiles of 64 chunk maps composed in parallel)
@@ -3052,19 +3276,19 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
         const size_t ntile = (size_t)b->n_chunks / 64 + (size_t)b->n + 2;
         HIPCHK(b->Gg.ensure(ntile * m->NP));
         HIPCHK(b->tstate.ensure(ntile));
-        hipLaunchKernelGGL(k_tb_group, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->G.p,
+        hipLaunchKernelGGL(k_tb_group<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->G.p,
                            b->Gg.p);
-        hipLaunchKernelGGL(k_tb_scan_top, dim3(b->n), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->Gg.p,
+        hipLaunchKernelGGL(k_tb_scan_top<uint8_t>, dim3(b->n), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->Gg.p,
                            (const int *)b->last_state.p, b->tstate.p, b->paths.p);
-        hipLaunchKernelGGL(k_tb_scan_tiles, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
+        hipLaunchKernelGGL(k_tb_scan_tiles<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
                            (const uint8_t *)b->G.p, (const uint8_t *)b->tstate.p, b->bstate.p);
       } else {
-        hipLaunchKernelGGL(k_tb_scan, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
+        hipLaunchKernelGGL(k_tb_scan<uint8_t>, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
                            b->G.p, b->last_state.p, b->bstate.p, b->paths.p);
       }
     }
     if (b->n_chunks > 0)
-      hipLaunchKernelGGL(k_tb_fill, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv,
+      hipLaunchKernelGGL(k_tb_fill<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv,
                          b->n_chunks, b->d_chunk_iv.p, b->d_chunk0.p, b->TBW, b->tb.p, b->bstate.p,
                          b->paths.p);
     (void)hipEventRecord(b->ev[eV + 2], st);
@@ -3409,6 +3633,10 @@ int tehmm_batch_posterior_masksum(tehmm_batch_t *b, const double *mask, int64_t 
   DBuf<double> d_mask, d_out;
   HIPCHK(d_mask.upload(mask, (size_t)b->N));
   HIPCHK(d_out.alloc((size_t)rows));
+  if (b->N > kMaxStates)
+    hipLaunchKernelGGL(k_post_masksum_large, dim3(grid_for(rows * 64, 256, 256 * 32)), dim3(256), 0, 0, rows, b->N,
+                       (const double *)(b->post.p + (size_t)row0 * b->N), (const double *)d_mask.p, d_out.p);
+  else
   hipLaunchKernelGGL(k_post_masksum, dim3(grid_for(rows * 64, 256, 256 * 32)), dim3(256), 0, 0, rows, b->N,
                      (const double *)(b->post.p + (size_t)row0 * b->N), (const double *)d_mask.p, d_out.p);
   HIPCHK(hipGetLastError());
@@ -3485,13 +3713,84 @@ int tehmm_write_bed(const char *path, int append, const char *chrom, int64_t n, 
   return rc;
 }
 
+// Array-level Viterbi for 129 <= N <= 1024: k_vit_large on the frame, then the large traceback.
+static int viterbi_large(int64_t T, int N, const double *pi, const double *lt, const double *segRatios,
+                         const double *frame, int64_t *path, double *logprob) {
+  const LargeGeom lg = large_geom(N);
+  const int NP = lg.NP;
+  const bool wide_ptr = N > 256;
+  const size_t pb = wide_ptr ? 2 : 1;
+  std::vector<double> hlt((size_t)NP * NP, -INFINITY), hpi(NP, -INFINITY);
+  for (int i = 0; i < N; ++i) {
+    hpi[i] = pi[i];
+    for (int j = 0; j < N; ++j) hlt[(size_t)i * NP + j] = lt[(size_t)i * N + j];
+  }
+  const int64_t Tpad = (T + 63) & ~(int64_t)63;
+  const int64_t nch64 = T > 1 ? (T - 1 + TEHMM_TB_CHUNK - 1) / TEHMM_TB_CHUNK : 0;
+  if (nch64 > 0x7fffffff) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_viterbi: T too large");
+  const int nch = (int)nch64;
+  int64_t h_off[2] = {0, T}, h_pos0[2] = {0, Tpad}, h_len[1] = {T}, h_chunk0[2] = {0, nch};
+  int h_order[1] = {0};
+  std::vector<int> chunk_iv((size_t)nch, 0);
+  DBuf<double> d_lt, d_pi, d_fr, d_r, d_lp;
+  DBuf<int64_t> d_off, d_pos0, d_len, d_chunk0, d_paths;
+  DBuf<int> d_order, d_chunk_iv, d_last;
+  DBuf<uint8_t> d_tb, d_G, d_bs, d_Gg, d_ts;
+  HIPCHK(d_lt.upload(hlt.data(), hlt.size()));
+  HIPCHK(d_pi.upload(hpi.data(), hpi.size()));
+  HIPCHK(d_fr.upload(frame, (size_t)T * N));
+  if (segRatios) {
+    std::vector<double> r((size_t)Tpad, 0.0);
+    std::copy(segRatios, segRatios + T, r.begin());
+    HIPCHK(d_r.upload(r.data(), r.size()));
+  }
+  HIPCHK(d_off.upload(h_off, 2));
+  HIPCHK(d_pos0.upload(h_pos0, 2));
+  HIPCHK(d_len.upload(h_len, 1));
+  HIPCHK(d_chunk0.upload(h_chunk0, 2));
+  HIPCHK(d_order.upload(h_order, 1));
+  HIPCHK(d_chunk_iv.upload(chunk_iv.data(), chunk_iv.size()));
+  HIPCHK(d_paths.alloc((size_t)T));
+  HIPCHK(d_tb.alloc((size_t)(Tpad + 1) * NP * pb));
+  HIPCHK(d_G.alloc((size_t)(nch + 1) * NP * pb));
+  HIPCHK(hipMemset(d_G.p, 0, (size_t)(nch + 1) * NP * pb));
+  HIPCHK(d_bs.alloc(((size_t)nch + 1) * pb));
+  HIPCHK(d_last.alloc(1));
+  HIPCHK(d_lp.alloc(1));
+  IntervalTab iv;
+  iv.order = d_order.p;
+  iv.pos0 = d_pos0.p;
+  iv.len = d_len.p;
+  iv.out0 = d_off.p;
+  iv.n = 1;
+  EmisTab em;
+  std::memset(&em, 0, sizeof(em));
+  int rc;
+  if (wide_ptr) {
+    launch_vit_large<uint16_t>(iv, em, lg, 1, segRatios != nullptr, true, d_lt.p, d_pi.p, d_r.p, d_fr.p, d_tb.p,
+                               d_last.p, d_lp.p, 0);
+    rc = traceback_large<uint16_t>(iv, 1, h_chunk0, nch, d_chunk_iv.p, d_chunk0.p, N, NP, d_tb.p, d_G.p, d_bs.p, d_Gg,
+                                   d_ts, d_last.p, d_paths.p, 0);
+  } else {
+    launch_vit_large<uint8_t>(iv, em, lg, 1, segRatios != nullptr, true, d_lt.p, d_pi.p, d_r.p, d_fr.p, d_tb.p,
+                              d_last.p, d_lp.p, 0);
+    rc = traceback_large<uint8_t>(iv, 1, h_chunk0, nch, d_chunk_iv.p, d_chunk0.p, N, NP, d_tb.p, d_G.p, d_bs.p, d_Gg,
+                                  d_ts, d_last.p, d_paths.p, 0);
+  }
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(path, d_paths.p, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(logprob, d_lp.p, sizeof(double), hipMemcpyDeviceToHost));
+  return TEHMM_OK;
+}
+
 // Array-level Viterbi: one interval, frame input, through the same kernel + traceback.
 int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const double *segRatios,
                   const double *frame, int64_t *path, double *logprob) {
   if (T < 0 || N <= 0 || !pi || !lt || !frame || !path || !logprob)
     return fail(TEHMM_ERR_ARG, "tehmm_viterbi: bad argument");
-  if (N > kMaxStates) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_viterbi: N > 128");
+  if (N > TEHMM_LARGE_MAX) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_viterbi: N > 1024");
   if (T == 0) return TEHMM_OK;
+  if (N > kMaxStates) return viterbi_large(T, N, pi, lt, segRatios, frame, path, logprob);
   const int NP = pad_states(N);
   std::vector<double> hlt((size_t)NP * NP, -INFINITY), hpi(NP, -INFINITY);
   for (int i = 0; i < N; ++i) {
@@ -3550,15 +3849,15 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
     if (segRatios) { VIT_LAUNCH(2, true); } else { VIT_LAUNCH(2, false); }
   }
 #undef VIT_LAUNCH
-  allow_lds(k_tb_compose, 4 * TEHMM_TB_STAGE);
-  allow_lds(k_tb_fill, 4 * TEHMM_TB_STAGE);
+  allow_lds(k_tb_compose<uint8_t>, 4 * TEHMM_TB_STAGE);
+  allow_lds(k_tb_fill<uint8_t>, 4 * TEHMM_TB_STAGE);
   if (nch > 0)
-    hipLaunchKernelGGL(k_tb_compose, dim3((nch + 3) / 4), dim3(256), 4 * tb_stage_bytes(NP), 0, iv, d_chunk_iv.p, d_chunk0.p,
+    hipLaunchKernelGGL(k_tb_compose<uint8_t>, dim3((nch + 3) / 4), dim3(256), 4 * tb_stage_bytes(NP), 0, iv, d_chunk_iv.p, d_chunk0.p,
                        nch, N, NP, NP, d_tb.p, d_G.p);
-  hipLaunchKernelGGL(k_tb_scan, dim3(1), dim3(64), 0, 0, iv, d_chunk0.p, NP, d_G.p, d_last.p, d_bs.p,
+  hipLaunchKernelGGL(k_tb_scan<uint8_t>, dim3(1), dim3(64), 0, 0, iv, d_chunk0.p, NP, d_G.p, d_last.p, d_bs.p,
                      d_paths.p);
   if (nch > 0)
-    hipLaunchKernelGGL(k_tb_fill, dim3((nch + 3) / 4), dim3(256), 4 * tb_stage_bytes(NP), 0, iv, nch,
+    hipLaunchKernelGGL(k_tb_fill<uint8_t>, dim3((nch + 3) / 4), dim3(256), 4 * tb_stage_bytes(NP), 0, iv, nch,
                        d_chunk_iv.p, d_chunk0.p, NP, d_tb.p, d_bs.p, d_paths.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(path, d_paths.p, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -4232,14 +4531,19 @@ static int estep_accumulate(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, 
   return TEHMM_OK;
 }
 
-int64_t tehmm_model_stats_size(const tehmm_model_t *m) { return m ? stats_size(m->NP, m->R) : 0; }
+int64_t tehmm_model_stats_size(const tehmm_model_t *m) {
+  if (m && m->large) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_stats_size: no device-resident statistics for N > 128");
+  return m ? stats_size(m->NP, m->R) : 0;
+}
 
 int tehmm_estep_batch_device(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double *dev_stats,
                              double *logprob_sum) {
   if (!m || !b || !dev_stats || !logprob_sum)
     return fail(TEHMM_ERR_ARG, "tehmm_estep_batch_device: NULL argument");
   if (m->K != b->K) return fail(TEHMM_ERR_ARG, "tehmm_estep_batch_device: model/batch track count differ");
-  if (m->N > 128) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch_device: N > 128");
+  if (m->N > 128)
+    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch_device: N > 128 (the E-step of such a model runs on the "
+                                       "array-level entry points)");
   double lp = 0.0;
   int dead = 0;
   int rc = estep_accumulate(m, b, use_ratios, dev_stats, &lp, &dead);
@@ -4266,7 +4570,9 @@ int tehmm_estep_batch(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double
   if (!m || !b || !start || !trans || !obsStats || !logprob_sum)
     return fail(TEHMM_ERR_ARG, "tehmm_estep_batch: NULL argument");
   if (m->K != b->K) return fail(TEHMM_ERR_ARG, "tehmm_estep_batch: model/batch track count differ");
-  if (m->N > 128) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch: N > 128");
+  if (m->N > 128)
+    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch: N > 128 (the E-step of such a model runs on the array-level "
+                                       "entry points)");
   *logprob_sum = 0.0;
   if (b->n == 0 || b->total == 0) return TEHMM_OK;
   const int N = m->N, NP = m->NP, K = m->K, S = m->S;

@@ -584,47 +584,58 @@ __device__ __forceinline__ void tb_stage(const uint8_t *tb, int TBW, int64_t row
   for (int i = lane; i < nd; i += TEHMM_WAVE) d32[i] = src[i];
 }
 
+// PtrT: uint8_t pointers, or uint16_t for N > 256 (tehmm_large.hip.h); TBW counts pointers per row, the stage is sized
+// in bytes.  MS states per lane: two for N <= 128, (N + 63) / 64 for the large kernels.
+template <typename PtrT, int MS = 2>
 __global__ __launch_bounds__(256) void k_tb_compose(IntervalTab iv, const int *chunk_iv,
                                                     const int64_t *chunk0, int n_chunks, int N, int NP, int TBW,
-                                                    const uint8_t *tb, uint8_t *G) {
+                                                    const PtrT *tb, PtrT *G) {
   extern __shared__ uint8_t tb_lds[];
   __builtin_amdgcn_s_setprio(TEHMM_PRIO_HI);      // latency kernel: issue ahead of co-resident throughput waves
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 4 + w;
   if (c >= n_chunks) return;
-  const int stage = tb_stage_bytes(TBW);
-  uint8_t *rows = tb_lds + w * stage;
+  const int RB = TBW * (int)sizeof(PtrT);               // bytes per pointer row
+  const int stage = tb_stage_bytes(RB);
+  PtrT *rows = (PtrT *)(tb_lds + w * stage);
   const int id = chunk_iv[c];
   const int64_t T = iv.len[id], p0 = iv.pos0[id];
   const int64_t cl = c - chunk0[id];
   const int64_t lo = cl * TEHMM_TB_CHUNK;
   const int64_t hi = min(lo + TEHMM_TB_CHUNK, T - 1);
-  const int rps = stage / TBW;                          // rows per stage
-  int s0 = lane, s1 = lane + TEHMM_WAVE;                // up to two states per lane (N <= 128)
+  const int rps = stage / RB;                           // rows per stage
+  int st[MS];
+#pragma unroll
+  for (int k = 0; k < MS; ++k) st[k] = lane + TEHMM_WAVE * k;
   for (int64_t top = hi; top > lo; top -= rps) {
     const int64_t bot = max(lo, top - rps);             // pointers t in (bot, top]
     const int n = (int)(top - bot);
     __builtin_amdgcn_wave_barrier();
-    tb_stage(tb, TBW, p0 + bot + 1, n, rows, lane);
+    tb_stage((const uint8_t *)tb, RB, p0 + bot + 1, n, (uint8_t *)rows, lane);
     __builtin_amdgcn_wave_barrier();
     for (int r = n - 1; r >= 0; --r) {
-      if (s0 < N) s0 = rows[r * TBW + s0];
-      if (s1 < N) s1 = rows[r * TBW + s1];
+#pragma unroll
+      for (int k = 0; k < MS; ++k)
+        if (st[k] < N) st[k] = rows[r * TBW + st[k]];
     }
   }
-  if (lane < N) G[(int64_t)c * NP + lane] = (uint8_t)s0;
-  if (lane + TEHMM_WAVE < N) G[(int64_t)c * NP + lane + TEHMM_WAVE] = (uint8_t)s1;
+#pragma unroll
+  for (int k = 0; k < MS; ++k)
+    if (lane + TEHMM_WAVE * k < N) G[(int64_t)c * NP + lane + TEHMM_WAVE * k] = (PtrT)st[k];
 }
 // scan: sequential over the chunks of one interval (T/C dependent byte lookups)
 // One wave per interval.  The chain over the interval's chunks (state at the chunk end -> state at its
 // start) is a dependent walk; 64 chunk maps at a time are fetched cooperatively into LDS so that the walk
 // itself only touches LDS (it used to pay one global-memory latency per chunk, ~16 ms next to an
 // HBM-bound kernel for a 2 Mb interval).
-__global__ __launch_bounds__(64) void k_tb_scan(IntervalTab iv, const int64_t *chunk0, int NP, const uint8_t *G,
-                                                const int *last_state, uint8_t *bstate, int64_t *paths) {
+// DIRECT (the kernels of tehmm_large.hip.h, NP > 132): the chunk maps are too wide to stage 64 of them in LDS; lane 0
+// reads the one element it needs from global memory instead.
+template <typename PtrT, bool DIRECT = false>
+__global__ __launch_bounds__(64) void k_tb_scan(IntervalTab iv, const int64_t *chunk0, int NP, const PtrT *G,
+                                                const int *last_state, PtrT *bstate, int64_t *paths) {
   __builtin_amdgcn_s_setprio(TEHMM_PRIO_HI);      // latency kernel: issue ahead of co-resident throughput waves
   __shared__ uint8_t rows[64 * 136];   // NP <= 132
-  __shared__ uint8_t bst[64];
+  __shared__ PtrT bst[64];
   const int id = blockIdx.x;
   const int lane = threadIdx.x;
   if (id >= iv.n) return;
@@ -636,15 +647,32 @@ __global__ __launch_bounds__(64) void k_tb_scan(IntervalTab iv, const int64_t *c
     if (lane == 0) paths[iv.out0[id]] = s;
     return;
   }
+  if constexpr (DIRECT) {
+    for (int64_t hi = nc; hi > 0; hi -= 64) {
+      const int64_t lo = hi > 64 ? hi - 64 : 0;
+      const int n = (int)(hi - lo);
+      if (lane == 0) {
+        for (int c = n - 1; c >= 0; --c) {
+          bst[c] = (PtrT)s;
+          s = G[(c0 + lo + c) * NP + s];
+        }
+      }
+      __syncthreads();
+      s = __shfl(s, 0);
+      if (lane < n) bstate[c0 + lo + lane] = bst[lane];
+      __syncthreads();
+    }
+    return;
+  }
   for (int64_t hi = nc; hi > 0; hi -= 64) {
     const int64_t lo = hi > 64 ? hi - 64 : 0;
     const int n = (int)(hi - lo);
-    const uint8_t *src = G + (c0 + lo) * NP;
+    const uint8_t *src = (const uint8_t *)G + (c0 + lo) * NP;
     for (int i = lane; i < n * NP; i += 64) rows[i] = src[i];
     __syncthreads();
     if (lane == 0) {
       for (int c = n - 1; c >= 0; --c) {
-        bst[c] = (uint8_t)s;
+        bst[c] = (PtrT)s;
         s = rows[c * NP + s];
       }
     }
@@ -659,8 +687,10 @@ __global__ __launch_bounds__(64) void k_tb_scan(IntervalTab iv, const int64_t *c
 // [nc - 64 ty - 64, nc - 64 ty)), are composed in parallel (k_tb_group: lane = state at the tile's upper end), one wave
 // per interval walks the tile maps (k_tb_scan_top), then every tile walks its own chunks from the state it was handed
 // (k_tb_scan_tiles).  Tile storage of interval id starts at chunk0[id] / 64 + id (never overlapping).
-__global__ __launch_bounds__(64) void k_tb_group(IntervalTab iv, const int64_t *chunk0, int NP, const uint8_t *G,
-                                                 uint8_t *Gg) {
+// (DIRECT: the lanes walk the chunk maps in global memory, up to 16 states each, see k_tb_scan)
+template <typename PtrT, bool DIRECT = false>
+__global__ __launch_bounds__(64) void k_tb_group(IntervalTab iv, const int64_t *chunk0, int NP, const PtrT *G,
+                                                 PtrT *Gg) {
   __shared__ uint8_t rows[64 * 136];
   const int id = blockIdx.x, ty = blockIdx.y, lane = threadIdx.x;
   if (id >= iv.n || iv.len[id] <= 0) return;
@@ -669,21 +699,38 @@ __global__ __launch_bounds__(64) void k_tb_group(IntervalTab iv, const int64_t *
   if (hi <= 0) return;
   const int64_t lo = hi > 64 ? hi - 64 : 0;
   const int n = (int)(hi - lo);
-  const uint8_t *src = G + (c0 + lo) * NP;
+  if constexpr (DIRECT) {
+    const int64_t tile = c0 / 64 + id + ty;
+    int st[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) st[k] = lane + 64 * k;
+    for (int c = n - 1; c >= 0; --c) {
+      const PtrT *row = G + (c0 + lo + c) * NP;
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (lane + 64 * k < NP) st[k] = row[st[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (lane + 64 * k < NP) Gg[tile * NP + lane + 64 * k] = (PtrT)st[k];
+    return;
+  }
+  const uint8_t *src = (const uint8_t *)G + (c0 + lo) * NP;
   for (int i = lane; i < n * NP; i += 64) rows[i] = src[i];
   __syncthreads();
   const int64_t tile = c0 / 64 + id + ty;
   for (int s0 = lane; s0 < NP; s0 += 64) {
     int s = s0;
     for (int c = n - 1; c >= 0; --c) s = rows[c * NP + s];
-    Gg[tile * NP + s0] = (uint8_t)s;
+    Gg[tile * NP + s0] = (PtrT)s;
   }
 }
-__global__ __launch_bounds__(64) void k_tb_scan_top(IntervalTab iv, const int64_t *chunk0, int NP, const uint8_t *Gg,
-                                                    const int *last_state, uint8_t *tstate, int64_t *paths) {
+template <typename PtrT, bool DIRECT = false>
+__global__ __launch_bounds__(64) void k_tb_scan_top(IntervalTab iv, const int64_t *chunk0, int NP, const PtrT *Gg,
+                                                    const int *last_state, PtrT *tstate, int64_t *paths) {
   __builtin_amdgcn_s_setprio(TEHMM_PRIO_HI);
   __shared__ uint8_t rows[64 * 136];
-  __shared__ uint8_t bst[64];
+  __shared__ PtrT bst[64];
   const int id = blockIdx.x, lane = threadIdx.x;
   if (id >= iv.n || iv.len[id] <= 0) return;
   int s = last_state[id];
@@ -695,14 +742,23 @@ __global__ __launch_bounds__(64) void k_tb_scan_top(IntervalTab iv, const int64_
   const int64_t nt = (nc + 63) / 64, t0 = c0 / 64 + id;
   for (int64_t lo = 0; lo < nt; lo += 64) {            // tiles ascend = positions descend
     const int n = (int)min((int64_t)64, nt - lo);
-    const uint8_t *src = Gg + (t0 + lo) * NP;
+    if constexpr (DIRECT) {
+      if (lane == 0) {
+        for (int c = 0; c < n; ++c) {
+          bst[c] = (PtrT)s;
+          s = Gg[(t0 + lo + c) * NP + s];
+        }
+      }
+    } else {
+    const uint8_t *src = (const uint8_t *)Gg + (t0 + lo) * NP;
     for (int i = lane; i < n * NP; i += 64) rows[i] = src[i];
     __syncthreads();
     if (lane == 0) {
       for (int c = 0; c < n; ++c) {
-        bst[c] = (uint8_t)s;
+        bst[c] = (PtrT)s;
         s = rows[c * NP + s];
       }
+    }
     }
     __syncthreads();
     s = __shfl(s, 0);
@@ -710,10 +766,11 @@ __global__ __launch_bounds__(64) void k_tb_scan_top(IntervalTab iv, const int64_
     __syncthreads();
   }
 }
-__global__ __launch_bounds__(64) void k_tb_scan_tiles(IntervalTab iv, const int64_t *chunk0, int NP, const uint8_t *G,
-                                                      const uint8_t *tstate, uint8_t *bstate) {
+template <typename PtrT, bool DIRECT = false>
+__global__ __launch_bounds__(64) void k_tb_scan_tiles(IntervalTab iv, const int64_t *chunk0, int NP, const PtrT *G,
+                                                      const PtrT *tstate, PtrT *bstate) {
   __shared__ uint8_t rows[64 * 136];
-  __shared__ uint8_t bst[64];
+  __shared__ PtrT bst[64];
   const int id = blockIdx.x, ty = blockIdx.y, lane = threadIdx.x;
   if (id >= iv.n || iv.len[id] <= 0) return;
   const int64_t c0 = chunk0[id], nc = chunk0[id + 1] - c0;
@@ -721,31 +778,43 @@ __global__ __launch_bounds__(64) void k_tb_scan_tiles(IntervalTab iv, const int6
   if (hi <= 0) return;
   const int64_t lo = hi > 64 ? hi - 64 : 0;
   const int n = (int)(hi - lo);
-  const uint8_t *src = G + (c0 + lo) * NP;
+  if constexpr (DIRECT) {
+    if (lane == 0) {
+      int s = tstate[c0 / 64 + id + ty];
+      for (int c = n - 1; c >= 0; --c) {
+        bst[c] = (PtrT)s;
+        s = G[(c0 + lo + c) * NP + s];
+      }
+    }
+  } else {
+  const uint8_t *src = (const uint8_t *)G + (c0 + lo) * NP;
   for (int i = lane; i < n * NP; i += 64) rows[i] = src[i];
   __syncthreads();
   if (lane == 0) {
     int s = tstate[c0 / 64 + id + ty];
     for (int c = n - 1; c >= 0; --c) {
-      bst[c] = (uint8_t)s;
+      bst[c] = (PtrT)s;
       s = rows[c * NP + s];
     }
+  }
   }
   __syncthreads();
   if (lane < n) bstate[c0 + lo + lane] = bst[lane];
 }
 // fill: one wave per chunk: pointer rows staged in LDS, lane 0 walks them and leaves the states in LDS, the
 // wave writes the int64 path coalesced
+template <typename PtrT>
 __global__ __launch_bounds__(256) void k_tb_fill(IntervalTab iv, int n_chunks, const int *chunk_iv, const int64_t *chunk0,
-                                                 int TBW, const uint8_t *tb, const uint8_t *bstate, int64_t *paths) {
+                                                 int TBW, const PtrT *tb, const PtrT *bstate, int64_t *paths) {
   extern __shared__ uint8_t tb_lds[];
-  __shared__ uint8_t walked[4][TEHMM_TB_CHUNK];
+  __shared__ PtrT walked[4][TEHMM_TB_CHUNK];
   __builtin_amdgcn_s_setprio(TEHMM_PRIO_HI);      // latency kernel: issue ahead of co-resident throughput waves
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 4 + w;
   if (c >= n_chunks) return;
-  const int stage = tb_stage_bytes(TBW);
-  uint8_t *rows = tb_lds + w * stage;
+  const int RB = TBW * (int)sizeof(PtrT);               // bytes per pointer row
+  const int stage = tb_stage_bytes(RB);
+  PtrT *rows = (PtrT *)(tb_lds + w * stage);
   const int id = chunk_iv[c];
   const int64_t T = iv.len[id], p0 = iv.pos0[id];
   const int64_t cl = c - chunk0[id];
@@ -754,17 +823,17 @@ __global__ __launch_bounds__(256) void k_tb_fill(IntervalTab iv, int n_chunks, c
   int64_t *out = paths + iv.out0[id];
   int s = bstate[c];
   if (lane == 0) out[hi] = s;
-  const int rps = stage / TBW;
+  const int rps = stage / RB;
   for (int64_t top = hi; top > lo; top -= rps) {
     const int64_t bot = max(lo, top - rps);             // pointers t in (bot, top] give the states at bot .. top - 1
     const int n = (int)(top - bot);
     __builtin_amdgcn_wave_barrier();
-    tb_stage(tb, TBW, p0 + bot + 1, n, rows, lane);
+    tb_stage((const uint8_t *)tb, RB, p0 + bot + 1, n, (uint8_t *)rows, lane);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
       for (int r = n - 1; r >= 0; --r) {
         s = rows[r * TBW + s];
-        walked[w][r] = (uint8_t)s;                      // state at position bot + r
+        walked[w][r] = (PtrT)s;                         // state at position bot + r
       }
     }
     __builtin_amdgcn_wave_barrier();

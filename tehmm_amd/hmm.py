@@ -197,7 +197,7 @@ class MultitrackHmm(BaseHMM):
 
     def _can_fuse(self, tables):
         from . import _lib
-        if self.n_components > _lib.load().tehmm_max_states():
+        if self.n_components > _lib.load().tehmm_max_states_any():
             return False
         for t in tables:
             a = t.getNumPyArray() if isinstance(t, TrackTable) else t
