@@ -14,7 +14,8 @@
 //     exists in memory, only one row in 64 is kept for the fix-up chain's direction check.
 // Per position: forward 12 B in + 288 B out, backward 12 + 288 B in + 280 B out (was 2 938 B).
 //
-// Both passes run on the fp64 matrix cores in the transposed form of k_fb_mfma (tehmm_lane.hip.h):
+// Both passes run on the fp64 matrix cores.  Per step and tile of 16 items the product is computed TRANSPOSED,
+//     D'[state j][item i] = sum_k  T[j][k] * V[k][i],     T[j][k] = A[k][j] (forward) or A[j][k] (backward):
 // lane l owns item (l & 15) of its 16-item tile and the states (l >> 4) + 4 s, the accumulator layout of
 // v_mfma_f64_16x16x4_f64 is the B-operand layout of the next step.  Tables are stored so that a lane's
 // states are contiguous: row r, quarter kq -> KSP doubles [P[kq], P[kq + 4], ..., c] (the spare slot of the
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256) void k_fused_rowindex(IntervalTab iv, LaneGeom
 }
 
 // ------------------------------------------------------------------------------------------
-// Forward pass.  Same contract as k_fb_lane<NT, 0> / k_fb_mfma<NT, 0>: alpha' rows of the official range
+// Forward pass.  Same contract as k_fb_lane<NT, 0>: alpha' rows of the official range
 // (item-interleaved), pre / end vectors, cumulative log-scale records; the emission rows are computed here.
 // Extended step e <-> position t0 - Wu + e; the pass covers e = 0 .. L + Wu - 1.
 // ------------------------------------------------------------------------------------------

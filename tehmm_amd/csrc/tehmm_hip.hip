@@ -1255,6 +1255,42 @@ static int spec_chunk_size() {
   return std::max(64, (cs + 63) & ~63);
 }
 
+// The environment knobs of the N <= 128 evaluation and of the fused E-step, read once per call (tests flip them between
+// calls).  -1: not set (a negative TEHMM_DEFER counts as not set).
+struct EvalKnobs {
+  int spec_chunk;       // TEHMM_SPEC_CHUNK: chunk length of the chunk-parallel passes (0: none)
+  int lane_sub;         // TEHMM_LANE_SUB: item length of the lane = item passes (0: none; -1: by batch size)
+  int lane_warmup;      // TEHMM_LANE_WARMUP: forward / backward warm-up (-1: probed)
+  bool lane_probe;      // TEHMM_LANE_PROBE=0: warm-up 64 without the probe
+  bool lane_vit;        // TEHMM_LANE_VIT=0: no lane = item exact Viterbi pass
+  bool lane_p0;         // TEHMM_LANE_P0=0: P0 as the fp64 lane = state pass
+  bool fused;           // TEHMM_FUSED=0: the round-1 posterior pipeline
+  bool device_place;    // TEHMM_DEVICE_PLACE=0: binade placement on the host
+  bool soft_ties;       // TEHMM_SOFT_TIES=0: every rounding tie ends a piece of the quantised pass
+  int emis_split;       // TEHMM_EMIS_SPLIT: three-wave emission + gain pass on (1) / off (0); -1: by batch size
+  int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
+};
+
+static EvalKnobs read_eval_knobs() {
+  auto num = [](const char *name, int unset) {
+    const char *s = std::getenv(name);
+    return s ? std::atoi(s) : unset;
+  };
+  EvalKnobs k;
+  k.spec_chunk = spec_chunk_size();
+  k.lane_sub = std::getenv("TEHMM_LANE_SUB") ? std::max(0, num("TEHMM_LANE_SUB", 0)) : -1;
+  k.lane_warmup = std::getenv("TEHMM_LANE_WARMUP") ? std::max(1, num("TEHMM_LANE_WARMUP", 1)) : -1;
+  k.lane_probe = num("TEHMM_LANE_PROBE", 1) != 0;
+  k.lane_vit = num("TEHMM_LANE_VIT", 1) != 0;
+  k.lane_p0 = num("TEHMM_LANE_P0", 1) != 0;
+  k.fused = num("TEHMM_FUSED", 1) != 0;
+  k.device_place = num("TEHMM_DEVICE_PLACE", 1) != 0;
+  k.soft_ties = num("TEHMM_SOFT_TIES", 1) != 0;
+  k.emis_split = std::getenv("TEHMM_EMIS_SPLIT") ? (num("TEHMM_EMIS_SPLIT", 0) != 0 ? 1 : 0) : -1;
+  k.defer = num("TEHMM_DEFER", -1);
+  return k;
+}
+
 static int spec_prepare(tehmm_batch *b, const tehmm_model *m, int CS) {
   SpecWork &sw = b->sw;
   if (sw.CS == CS && sw.N == m->N && sw.rows.p) return TEHMM_OK;
@@ -1308,7 +1344,14 @@ static int spec_prepare(tehmm_batch *b, const tehmm_model *m, int CS) {
 // sums are enough: a wrong or risky guess only sends that chunk to the sequential chain -- the chain's
 // check demands every live value inside the chunk's binade and, from the recorded minima, up to the
 // landing position).  The margin (512 + 2e-5 |V|; float P0 sums are good to ~2e-6) only keeps chunks
-// that end within it of a binade boundary from being speculated in the wrong binade.
+// that end within it of a binade boundary from being speculated in the wrong binade.  The host placement here and the
+// device placement (launch_vit_place) apply the same rule: these two constants.
+constexpr double kSpecMarginRel = 2e-5;
+// A chunk that crosses into the next binade is quantised for the binade it ends in: the exact chain runs it up to the
+// crossing and is then verified against its rows like anywhere else (the check demands every live value inside the
+// binade, so nothing before the crossing is ever adopted).
+constexpr bool kSpecCross = true;
+
 static void spec_assign_binades(const tehmm_batch *b, const std::vector<double> &gain, std::vector<int> &e) {
   const SpecWork &sw = b->sw;
   e.assign((size_t)std::max(1, sw.n_chunks), TEHMM_SPEC_NONE);
@@ -1320,18 +1363,13 @@ static void spec_assign_binades(const tehmm_batch *b, const std::vector<double> 
       v = ve;
       const bool full = sw.h_t0[(size_t)c] + sw.CS <= b->h_len[i];
       if (c == sw.h_first[i] || !full || !(g == g) || !(g < 0.0)) continue;
-      static const double rel = std::getenv("TEHMM_SPEC_MARGIN") ? std::atof(std::getenv("TEHMM_SPEC_MARGIN")) : 2e-5;
-      const double margin = 512.0 + rel * std::fabs(ve);
+      const double margin = 512.0 + kSpecMarginRel * std::fabs(ve);
       const double lo = std::fabs(vs) - margin, hi = std::fabs(ve) + margin;
       if (!(lo > 0.0)) continue;
       int ex = 0, exh = 0;
       (void)std::frexp(lo, &ex);          // lo = f * 2^ex, f in [0.5, 1)  ->  binade exponent ex - 1
       (void)std::frexp(hi, &exh);
-      // A chunk that crosses into the next binade is quantised for the binade it ends in: the exact chain
-      // runs it up to the crossing and is then verified against its rows like anywhere else (the check
-      // demands every live value inside the binade, so nothing before the crossing is ever adopted).
-      static const bool cross = !(std::getenv("TEHMM_SPEC_CROSS") && std::atoi(std::getenv("TEHMM_SPEC_CROSS")) == 0);
-      if (exh != ex && !(cross && exh == ex + 1)) continue;
+      if (exh != ex && !(kSpecCross && exh == ex + 1)) continue;
       const int be = exh - 1;
       if (be < TEHMM_SPEC_MIN_E) continue;
       e[(size_t)c] = be;
@@ -1383,13 +1421,13 @@ static LaneGeom lane_geom(const LaneWork &lw);
 
 // Item length L (L | CS, 64 | L).  Every wave owns 64 items; 512 positions per item keep the warm-up
 // overhead below 20 %, 256 / 128 are used for small batches so that the 1024 SIMDs still get a wave each.
-// TEHMM_LANE_SUB overrides (0 disables the lane passes).
-static int lane_sub_size(int CS, int64_t total) {
+// TEHMM_LANE_SUB (knob >= 0) overrides (0 disables the lane passes).
+static int lane_sub_size(int CS, int64_t total, int knob) {
   if (CS <= 0) return 0;
   // (measured: 10 Mb in one interval runs the lane passes in 16.1 ms with 128-position items, 18.2 with 256)
   int L = total >= (int64_t)512 * 64 * 1024 ? 512 : (total >= (int64_t)256 * 64 * 1024 ? 256 : 128);
-  if (const char *s = std::getenv("TEHMM_LANE_SUB")) {
-    L = std::atoi(s);
+  if (knob >= 0) {
+    L = knob;
     if (L <= 0) return 0;
     L = std::max(64, (L + 63) & ~63);
   }
@@ -1583,52 +1621,45 @@ static int vit_lane_upload_args(tehmm_batch *b, const VitChunks &vc, hipStream_t
 // n_work_dev != nullptr: the number of work units is read on the device (tehmm_place.hip.h) and n_work is only the
 // upper bound the grid is sized for; tabs / e0: the quantised tables and the binade of the first one
 template <int NT>
-static void launch_vit_lane(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const VitChunks &vc,
-                            bool quant, bool ratio, int Wu, int n_work, const double *tabs, int e0, const int *n_work_dev,
+static void launch_vit_lane(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const VitChunks &vc, bool ratio,
+                            bool soft, int Wu, int n_work, const double *tabs, int e0, const int *n_work_dev,
                             hipStream_t st) {
   LaneWork &lw = b->lw;
   const LaneGeom lg = lane_geom(lw);
   lw.soft_ties = 0;
   if (n_work <= 0) return;
-  // round 4: the outputs of a step split over the three waves of a workgroup (tehmm_lane3.hip.h); TEHMM_P2_SPLIT=0
-  // keeps the one-wave kernel (which also serves the smallest models)
   if constexpr (NT >= 12) {
-    const bool split = !(std::getenv("TEHMM_P2_SPLIT") && std::atoi(std::getenv("TEHMM_P2_SPLIT")) == 0);
-    if (quant && split) {
-      constexpr int NW = TEHMM_P2_NW;
-      const size_t lds = Lane3Geom<NT, NW>::LDS_BYTES;
-      if constexpr (NT <= TEHMM_RATIO_LANE_MAX) if (ratio) {
-        allow_lds(k_vit_lane3<NT, NW, true>, lds);
-        hipLaunchKernelGGL((k_vit_lane3<NT, NW, true>), dim3(n_work), dim3(64 * NW), lds, st, iv, lg,
-                           (const VitChunks *)lw.d_vc.p, (const VitItems *)lw.d_vi.p, m->N, Wu, (const int *)lw.wk_g.p,
-                           (const int *)lw.wk_e.p, n_work, tabs, e0, (const double *)lw.B.p, b->tb.p,
-                           (const double *)b->ratios.p, (const int *)lw.wk_items.p, n_work_dev);
-        return;
-      }
-      // soft ties (TEHMM_SOFT_TIES=0: every rounding tie ends a piece, as in rounds 2 and 3)
-      const bool soft = !(std::getenv("TEHMM_SOFT_TIES") && std::atoi(std::getenv("TEHMM_SOFT_TIES")) == 0);
-      lw.soft_ties = soft ? 1 : 0;
-      allow_lds(k_vit_lane3<NT, NW, false>, lds);
-      hipLaunchKernelGGL((k_vit_lane3<NT, NW, false>), dim3(n_work), dim3(64 * NW), lds, st, iv, lg,
+    // round 4: the outputs of a step split over the three waves of a workgroup (tehmm_lane3.hip.h)
+    constexpr int NW = TEHMM_P2_NW;
+    const size_t lds = Lane3Geom<NT, NW>::LDS_BYTES;
+    if constexpr (NT <= TEHMM_RATIO_LANE_MAX) if (ratio) {
+      allow_lds(k_vit_lane3<NT, NW, true>, lds);
+      hipLaunchKernelGGL((k_vit_lane3<NT, NW, true>), dim3(n_work), dim3(64 * NW), lds, st, iv, lg,
                          (const VitChunks *)lw.d_vc.p, (const VitItems *)lw.d_vi.p, m->N, Wu, (const int *)lw.wk_g.p,
                          (const int *)lw.wk_e.p, n_work, tabs, e0, (const double *)lw.B.p, b->tb.p,
-                         (const double *)nullptr, (const int *)lw.wk_items.p, n_work_dev, lw.soft_ties);
+                         (const double *)b->ratios.p, (const int *)lw.wk_items.p, n_work_dev);
       return;
     }
-  }
-  const dim3 grid((n_work + 3) / 4);
-  if constexpr (NT <= TEHMM_RATIO_LANE_MAX) if (quant && ratio) {
-    hipLaunchKernelGGL((k_vit_lane<NT, true, true>), grid, dim3(256), 0, st, iv, lg, (const VitChunks *)lw.d_vc.p,
-                       (const VitItems *)lw.d_vi.p, m->N, Wu,
-                       (const int *)lw.wk_g.p, (const int *)lw.wk_e.p, n_work, tabs, e0,
-                       (const double *)lw.B.p, b->tb.p, (const double *)b->ratios.p, (const int *)lw.wk_items.p, n_work_dev);
-    return;
-  }
-  if (quant) {
+    // soft ties (TEHMM_SOFT_TIES=0: every rounding tie ends a piece, as in rounds 2 and 3)
+    lw.soft_ties = soft ? 1 : 0;
+    allow_lds(k_vit_lane3<NT, NW, false>, lds);
+    hipLaunchKernelGGL((k_vit_lane3<NT, NW, false>), dim3(n_work), dim3(64 * NW), lds, st, iv, lg,
+                       (const VitChunks *)lw.d_vc.p, (const VitItems *)lw.d_vi.p, m->N, Wu, (const int *)lw.wk_g.p,
+                       (const int *)lw.wk_e.p, n_work, tabs, e0, (const double *)lw.B.p, b->tb.p,
+                       (const double *)nullptr, (const int *)lw.wk_items.p, n_work_dev, lw.soft_ties);
+  } else {
+    // the one-wave kernel of the smallest models
+    const dim3 grid((n_work + 3) / 4);
+    if (ratio) {
+      hipLaunchKernelGGL((k_vit_lane<NT, true, true>), grid, dim3(256), 0, st, iv, lg, (const VitChunks *)lw.d_vc.p,
+                         (const VitItems *)lw.d_vi.p, m->N, Wu, (const int *)lw.wk_g.p, (const int *)lw.wk_e.p, n_work, tabs,
+                         e0, (const double *)lw.B.p, b->tb.p, (const double *)b->ratios.p, (const int *)lw.wk_items.p,
+                         n_work_dev);
+      return;
+    }
     hipLaunchKernelGGL((k_vit_lane<NT, true>), grid, dim3(256), 0, st, iv, lg, (const VitChunks *)lw.d_vc.p,
-                       (const VitItems *)lw.d_vi.p, m->N, Wu,
-                       (const int *)lw.wk_g.p, (const int *)lw.wk_e.p, n_work, tabs, e0,
-                       (const double *)lw.B.p, b->tb.p, (const double *)nullptr, (const int *)lw.wk_items.p, n_work_dev);
+                       (const VitItems *)lw.d_vi.p, m->N, Wu, (const int *)lw.wk_g.p, (const int *)lw.wk_e.p, n_work, tabs,
+                       e0, (const double *)lw.B.p, b->tb.p, (const double *)nullptr, (const int *)lw.wk_items.p, n_work_dev);
   }
 }
 
@@ -1655,12 +1686,11 @@ static int launch_vit_place(tehmm_batch *b, const tehmm_model *m, const Interval
                             int *n_work_max) {
   LaneWork &lw = b->lw;
   SpecWork &sw = b->sw;
-  static const double rel = std::getenv("TEHMM_SPEC_MARGIN") ? std::atof(std::getenv("TEHMM_SPEC_MARGIN")) : 2e-5;
-  static const int cross = !(std::getenv("TEHMM_SPEC_CROSS") && std::atoi(std::getenv("TEHMM_SPEC_CROSS")) == 0) ? 1 : 0;
   const LaneGeom lg = lane_geom(lw);
   hipLaunchKernelGGL(k_vit_place_chunks, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, (const int64_t *)sw.first.p,
                      (const int64_t *)sw.t0.p, (const int64_t *)lw.ifirst.p, b->n, CS, lw.L, (const double *)lw.vgain.p,
-                     (const int *)m->qok[ratio ? 1 : 0].p, rel, cross, sw.e.p, sw.gain.p);
+                     (const int *)m->qok[ratio ? 1 : 0].p, kSpecMarginRel, kSpecCross ? 1 : 0, sw.e.p,
+                     sw.gain.p);
   const int gb = (lw.n_groups + 255) / 256;
   hipLaunchKernelGGL(k_vit_place_count, dim3(std::max(1, gb)), dim3(256), 0, st, lg, (const int64_t *)sw.first.p,
                      (const int *)sw.e.p, CS, lw.place.p, lw.gclass.p);
@@ -1677,12 +1707,8 @@ static void launch_vit_stitch(tehmm_batch *b, const tehmm_model *m, const Interv
   LaneWork &lw = b->lw;
   hipLaunchKernelGGL((k_vit_stitch<NT>), dim3((vc.n + 3) / 4), dim3(256), 0, st, iv, lane_geom(lw), vc,
                      lane_vit_items(lw), m->N, lw.soft_ties);
-  const char *vl = std::getenv("TEHMM_VIT_RUNS");        // 0: one verification per chunk
-  if (vl && std::atoi(vl) == 0)
-    (void)hipMemsetAsync(vc.clink, 0, (size_t)vc.n * sizeof(int), st);
-  else
-    hipLaunchKernelGGL((k_vit_links<NT>), dim3((vc.n + 3) / 4), dim3(256), 0, st, iv, lane_geom(lw), vc,
-                       lane_vit_items(lw), m->N);
+  hipLaunchKernelGGL((k_vit_links<NT>), dim3((vc.n + 3) / 4), dim3(256), 0, st, iv, lane_geom(lw), vc,
+                     lane_vit_items(lw), m->N);
   hipLaunchKernelGGL(k_vit_runs, dim3(std::max(1, b->n)), dim3(64), 0, st, vc, b->n);
 }
 
@@ -1707,16 +1733,15 @@ static void launch_emis_lane(tehmm_batch *b, const tehmm_model *m, const Interva
 // emission rows (fp64 log rows for the exact Viterbi pass) and P0 in one pass
 template <int NT>
 static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em,
-                                  int CS, int Wu, bool ratio, hipStream_t st) {
+                                  int CS, int Wu, bool ratio, int emis_split, hipStream_t st) {
   LaneWork &lw = b->lw;
   // round 4: the states of a row split over the three waves of a unit (tehmm_lane3.hip.h); TEHMM_EMIS_SPLIT=0 keeps
-  // the one-wave kernel (which also serves the smallest models)
+  // the one-wave kernel (which also serves the smallest models); emis_split: that knob, -1 if not set
   if constexpr (NT >= 12) {
     // (measured, 36 states: 1.1 Mb 0.98 ms against 1.70; 100 Mb 17.4 against 14.7 -- three waves repeat the observation
     //  decode and the bookkeeping of a position, and a full GPU is short of vector issue slots, not of waves: the split
     //  form serves the batches that leave the one-wave kernel fewer than two waves per SIMD)
-    const char *es = std::getenv("TEHMM_EMIS_SPLIT");
-    const bool split = es ? std::atoi(es) != 0 : lw.n_groups < 2048;
+    const bool split = emis_split >= 0 ? emis_split != 0 : lw.n_groups < 2048;
     if (split) {
       constexpr int NW = TEHMM_P2_NW, NU = 2;
       const size_t lds3 = Emis3Geom<NT, NW, NU>::lds_bytes(em.lds_rows);
@@ -1763,27 +1788,17 @@ static void launch_fb_lane(tehmm_batch *b, const tehmm_model *m, const IntervalT
   LaneWork &lw = b->lw;
   const LaneGeom lg = lane_geom(lw);
   const dim3 grid((lw.n_groups + 3) / 4);
-  const dim3 gridm((unsigned)lw.n_groups);           // 4 tiles of 16 items per 256-thread block = one group
   const dim3 gridc((fc.n + 255) / 256);              // one thread per chunk
   const dim3 gridit((lw.n_items + 255) / 256);       // one thread per item
   const dim3 gridi(std::max(1, b->n));
-  // TEHMM_LANE_MFMA: 0 = the VALU form (default), 1 = the fp64 matrix-core form
-  const char *mfs = std::getenv("TEHMM_LANE_MFMA");
-  const bool mf = mfs && std::atoi(mfs) != 0;
-  const char *er = std::getenv("TEHMM_FB_RUNS");
-  const int extend = (er && std::atoi(er) == 0) ? 0 : 1;
   const EmisTab em = b->n > 256 ? without_lds_tables(em_in) : em_in;
   size_t lds = ((size_t)2 * 64 * (NT + 1) + 2 * 64 + NT + (size_t)em.lds_rows * NT + 8) * sizeof(double);
   allow_lds(k_fb_fix<NT, 0, false, true>, lds);
   allow_lds(k_fb_fix<NT, 1, false, true>, lds);
   hipStream_t sS = b->sB;
   // ---- forward
-  if (mf)
-    hipLaunchKernelGGL((k_fb_mfma<NT, 0>), gridm, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->A.p, lw.BH.p,
-                       lw.MS.p, lw.AL.p, lw.pre_f.p, lw.end_f.p, lw.slog32.p);
-  else
-    hipLaunchKernelGGL((k_fb_lane<NT, 0>), grid, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->AG.p, lw.BH.p,
-                       lw.MS.p, lw.AL.p, lw.pre_f.p, lw.end_f.p, lw.slog32.p);
+  hipLaunchKernelGGL((k_fb_lane<NT, 0>), grid, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->AG.p, lw.BH.p,
+                     lw.MS.p, lw.AL.p, lw.pre_f.p, lw.end_f.p, lw.slog32.p);
   (void)hipEventRecord(b->evX[0], st);
   (void)hipStreamWaitEvent(sS, b->evX[0], 0);
   hipLaunchKernelGGL((k_fb_itemlinks<NT>), gridit, dim3(256), 0, sS, lg, m->N, lw.pre_f.p, lw.end_f.p, lw.pre_b.p,
@@ -1791,24 +1806,20 @@ static void launch_fb_lane(tehmm_batch *b, const tehmm_model *m, const IntervalT
   hipLaunchKernelGGL((k_fb_stitch<NT>), gridc, dim3(256), 0, sS, iv, lg, fc, m->N, lw.slog32.p, lw.end_b.p,
                      lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, lw.ok_f.p, lw.ok_b.p, 1);
   hipLaunchKernelGGL(k_fb_runs, gridi, dim3(64), 0, sS, iv, fc, (const int *)lw.ok_f.p, (const int *)lw.ok_b.p,
-                     extend, 1);
+                     1);
   hipLaunchKernelGGL((k_fb_fix<NT, 0, false, true>), dim3(b->n), dim3(128), lds, sS, iv, em, fc, m->N, m->A.p,
                      m->lt.p, m->pi.p, (const double *)nullptr, lw.AL.p, b->fwd_lp.p, b->dead.p,
                      (double *)nullptr, (int *)nullptr, 1, b->sw.stats.p, lg, (const int *)lw.ok_f.p);
   (void)hipEventRecord(b->evX[1], sS);
   // ---- backward
-  if (mf)
-    hipLaunchKernelGGL((k_fb_mfma<NT, 1>), gridm, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->A.p, lw.BH.p,
-                       lw.MS.p, lw.BE.p, lw.pre_b.p, lw.end_b.p, (double *)nullptr);
-  else
-    hipLaunchKernelGGL((k_fb_lane<NT, 1>), grid, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->ATG.p, lw.BH.p,
-                       lw.MS.p, lw.BE.p, lw.pre_b.p, lw.end_b.p, (double *)nullptr);
+  hipLaunchKernelGGL((k_fb_lane<NT, 1>), grid, dim3(256), 0, st, iv, lg, m->N, fc.CS, Wu, m->ATG.p, lw.BH.p,
+                     lw.MS.p, lw.BE.p, lw.pre_b.p, lw.end_b.p, (double *)nullptr);
   hipLaunchKernelGGL((k_fb_itemlinks<NT>), gridit, dim3(256), 0, st, lg, m->N, lw.pre_f.p, lw.end_f.p, lw.pre_b.p,
                      lw.end_b.p, lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, 2);
   hipLaunchKernelGGL((k_fb_stitch<NT>), gridc, dim3(256), 0, st, iv, lg, fc, m->N, lw.slog32.p, lw.end_b.p,
                      lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, lw.ok_f.p, lw.ok_b.p, 2);
   hipLaunchKernelGGL(k_fb_runs, gridi, dim3(64), 0, st, iv, fc, (const int *)lw.ok_f.p, (const int *)lw.ok_b.p,
-                     extend, 2);
+                     2);
   (void)hipEventRecord(ev_mid, st);
   hipLaunchKernelGGL((k_fb_fix<NT, 1, false, true>), dim3(b->n), dim3(128), lds, st, iv, em, fc, m->N, m->A.p,
                      m->lt.p, m->pi.p, (const double *)nullptr, lw.BE.p, b->fwd_lp.p, b->dead.p,
@@ -1881,8 +1892,6 @@ static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalT
   const dim3 gridc((fc.n + 255) / 256);              // one thread per chunk
   const dim3 gridit((lw.n_items + 255) / 256);       // one thread per item
   const dim3 gridi(std::max(1, b->n));
-  const char *er = std::getenv("TEHMM_FB_RUNS");
-  const int extend = (er && std::atoi(er) == 0) ? 0 : 1;
   FusedOrder fo;
   if (int rcp = fused_prepare<NT>(b, m, iv, Wu, st, fo)) return rcp;
   FusedTab ft;
@@ -1913,8 +1922,7 @@ static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalT
                        lw.pre_b.p, lw.end_b.p, lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, 1);                                  \
     hipLaunchKernelGGL((k_fb_stitch<NT>), gridc, dim3(256), 0, st, iv, lg, fc, m->N, lw.slog32.p, lw.end_b.p,        \
                        lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, lw.ok_f.p, lw.ok_b.p, 1);                                    \
-    hipLaunchKernelGGL(k_fb_runs, gridi, dim3(64), 0, st, iv, fc, (const int *)lw.ok_f.p, (const int *)lw.ok_b.p,    \
-                       extend, 1);                                                                                   \
+    hipLaunchKernelGGL(k_fb_runs, gridi, dim3(64), 0, st, iv, fc, (const int *)lw.ok_f.p, (const int *)lw.ok_b.p, 1); \
     hipLaunchKernelGGL((k_fb_fix<NT, 0, false, true, true>), dim3(b->n), dim3(128), lds_c, st, iv, emc, fc, m->N,    \
                        m->A.p, m->lt.p, m->pi.p, (const double *)nullptr, (double *)nullptr, b->fwd_lp.p, b->dead.p, \
                        (double *)nullptr, (int *)nullptr, 1, b->sw.stats.p, lg, (const int *)lw.ok_f.p,              \
@@ -1945,7 +1953,7 @@ static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalT
   hipLaunchKernelGGL((k_fb_stitch<NT>), gridc, dim3(256), 0, st, iv, lg, fc, m->N, lw.slog32.p, lw.end_b.p,
                      lw.dl_f.p, lw.lr_f.p, lw.dl_b.p, lw.ok_f.p, lw.ok_b.p, 2);
   hipLaunchKernelGGL(k_fb_runs, gridi, dim3(64), 0, st, iv, fc, (const int *)lw.ok_f.p, (const int *)lw.ok_b.p,
-                     extend, 2);
+                     2);
   (void)hipEventRecord(ev_mid, st);
   if (estep) {
     const size_t lds_e = lds_c + (size_t)64 * (NT + 1) * sizeof(double);
@@ -1997,25 +2005,21 @@ static void launch_fb_fix(tehmm_batch *b, const tehmm_model *m, const IntervalTa
                      (double *)nullptr, (int *)nullptr, 1, b->sw.stats.p, LaneGeom(), (const int *)nullptr);
 }
 
-// -DTEHMM_DEV_NT=36: development builds that instantiate the fused kernels for one padded state
-// count only (seconds instead of minutes to compile); never used for the shipped library.
+// f(std::integral_constant<int, NT>{}) for the padded state count NP of a kernel family templated on NT; any other NP
+// calls nothing.  -DTEHMM_DEV_NT=36: development builds that instantiate the fused kernels for one padded state count
+// only (seconds instead of minutes to compile); never used for the shipped library.
+template <int... NTs, class F>
+static void nt_dispatch_of(int NP, F &&f) {
+  (void)((NP == NTs && (f(std::integral_constant<int, NTs>{}), true)) || ...);
+}
+template <class F>
+static void nt_dispatch(int NP, F &&f) {
 #ifdef TEHMM_DEV_NT
-#define TEHMM_NT_DISPATCH(NP_, CALL)                                                                \
-  switch (NP_) {                                                                                    \
-    case TEHMM_DEV_NT: CALL(TEHMM_DEV_NT); break;                                                   \
-    default: break;                                                                                 \
-  }
+  nt_dispatch_of<TEHMM_DEV_NT>(NP, f);
 #else
-#define TEHMM_NT_DISPATCH(NP_, CALL)                                                                \
-  switch (NP_) {                                                                                    \
-    case 4: CALL(4); break;   case 8: CALL(8); break;   case 12: CALL(12); break;                   \
-    case 16: CALL(16); break; case 20: CALL(20); break; case 24: CALL(24); break;                   \
-    case 28: CALL(28); break; case 32: CALL(32); break; case 36: CALL(36); break;                   \
-    case 40: CALL(40); break; case 48: CALL(48); break; case 56: CALL(56); break;                   \
-    case 64: CALL(64); break;                                                                       \
-    default: break;                                                                                 \
-  }
+  nt_dispatch_of<4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 48, 56, 64>(NP, f);
 #endif
+}
 
 
 
@@ -2110,9 +2114,6 @@ static int posterior_wide_finish(tehmm_batch *b, const tehmm_model *m, const Int
   for (;;) {
     HIPCHK(hipStreamSynchronize(st));
     const int Wu = w.pp_Wu;
-    if (std::getenv("TEHMM_SPEC_DEBUG"))
-      std::fprintf(stderr, "[tehmm wide] NPW %d L %d Wu %d: impossible rows in %d items, failed links %d of %d items\n", w.NPW, w.L,
-                   Wu, w.h_flags[0], w.h_flags[1], w.n_items);
     if (w.h_flags[0] > 0) return TEHMM_OK;             // impossible rows: the sequential kernels own their semantics
     if (w.h_flags[1] == 0) break;
     if (Wu >= kWuMax) return TEHMM_OK;                 // does not forget: sequential kernels
@@ -2470,37 +2471,6 @@ static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalT
   }
   hipLaunchKernelGGL(k_wide_tb_select, dim3(nc), dim3(256), 0, st, iv, vc, m->N, b->TBW, b->tb.p, (const uint8_t *)w.tb1.p,
                      (const uint8_t *)w.tb2.p, (const int64_t *)w.sel_from.p, (const int *)w.sel_hyp.p);
-  if (std::getenv("TEHMM_SPEC_DEBUG")) {
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<int> hok((size_t)nc), hnt((size_t)nc), hsel((size_t)nc);
-    HIPCHK(hipMemcpy(hok.data(), sw.ok.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hnt.data(), sw.ntie.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hsel.data(), w.sel_hyp.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
-    int n_spec = 0, n_ok = 0, n_sel[3] = {0, 0, 0};
-    long ties = 0;
-    for (int c = 0; c < nc; ++c) {
-      if (w.h_e[(size_t)c] == TEHMM_SPEC_NONE) continue;
-      ++n_spec;
-      n_ok += hok[(size_t)c] != 0;
-      ties += hnt[(size_t)c];
-      ++n_sel[hsel[(size_t)c] < 0 ? 2 : hsel[(size_t)c]];
-    }
-    std::fprintf(stderr, "[tehmm wide vit] chunks %d, speculated %d, usable %d, tie positions %ld, adopted h0 %d h1 %d none %d\n", nc,
-                 n_spec, n_ok, ties, n_sel[0], n_sel[1], n_sel[2]);
-    {
-      int st8[8];
-      HIPCHK(hipMemcpy(st8, sw.stats.p, sizeof(st8), hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "  failed checks %d: not in binade %d, leaves binade %d, no constant with matching parity %d\n", st8[2], st8[3],
-                   st8[4], st8[5]);
-    }
-    for (int e = 10; e < 30; ++e) {
-      int ne = 0, nok = 0, nsel = 0;
-      long nt = 0;
-      for (int c = 0; c < nc; ++c)
-        if (w.h_e[(size_t)c] == e) { ++ne; nok += hok[(size_t)c] != 0; nsel += hsel[(size_t)c] >= 0; nt += hnt[(size_t)c]; }
-      if (ne) std::fprintf(stderr, "  binade %d: chunks %d usable %d adopted %d tie positions %ld\n", e, ne, nok, nsel, nt);
-    }
-  }
   *done = true;
   return TEHMM_OK;
 }
@@ -2517,14 +2487,14 @@ static void launch_fb_probe(const tehmm_model *m, const IntervalTab &iv, const E
                      WMAX, steps + n);
 }
 
-static int fb_warmup(tehmm_batch *b, const tehmm_model *m, int LS, const IntervalTab &iv, const EmisTab &emg, int *out) {
-  if (const char *wus = std::getenv("TEHMM_LANE_WARMUP")) {
-    *out = std::min(LS, std::max(1, std::atoi(wus)));
+static int fb_warmup(tehmm_batch *b, const tehmm_model *m, int LS, const IntervalTab &iv, const EmisTab &emg,
+                     const EvalKnobs &kn, int *out) {
+  if (kn.lane_warmup > 0) {
+    *out = std::min(LS, kn.lane_warmup);
     return TEHMM_OK;
   }
   *out = std::min(LS, 64);
-  const char *pr = std::getenv("TEHMM_LANE_PROBE");
-  if ((pr && std::atoi(pr) == 0) || m->NP > 64) return TEHMM_OK;
+  if (!kn.lane_probe || m->NP > 64) return TEHMM_OK;
   LaneWork &lw = b->lw;
   if (lw.wu_model == m->uid && lw.wu_version == m->version && lw.wu_L == LS && lw.wu_val > 0) {
     *out = lw.wu_val;
@@ -2551,9 +2521,9 @@ static int fb_warmup(tehmm_batch *b, const tehmm_model *m, int LS, const Interva
   HIPCHK(lw.probe_iv.upload(p_iv.data(), p_iv.size()));
   HIPCHK(lw.probe_t0.upload(p_t0.data(), p_t0.size()));
   HIPCHK(lw.probe_steps.ensure(2 * NPR));
-#define CALL(NT_) launch_fb_probe<NT_>(m, iv, emg, NPR, WMAX, lw.probe_iv.p, lw.probe_t0.p, lw.probe_steps.p, b->sP)
-  TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
+  nt_dispatch(m->NP, [&](auto nt) {
+    launch_fb_probe<nt>(m, iv, emg, NPR, WMAX, lw.probe_iv.p, lw.probe_t0.p, lw.probe_steps.p, b->sP);
+  });
   HIPCHK(hipGetLastError());
   std::vector<int> steps(2 * NPR, 0);
   HIPCHK(hipMemcpyAsync(steps.data(), lw.probe_steps.p, steps.size() * sizeof(int), hipMemcpyDeviceToHost, b->sP));
@@ -2726,6 +2696,616 @@ static int eval_large(tehmm_model *m, tehmm_batch *b, int flags, double *viterbi
   return TEHMM_OK;
 }
 
+// ---- tehmm_eval_batch for N <= 128: the plan of one call, then the stages that enqueue it -----------------------
+// Events of the timing pairs: b->ev[eV + k] on the Viterbi stream, b->ev[eP + k] on the posterior stream (10 and 11:
+// starts of the lane posterior passes and of their backward half).
+constexpr int eV = 0, eP = 5;
+
+// Every path decision of one call, made before any stream work: plan_eval from the inputs and the knobs, plan_lanes
+// (behind spec_prepare, whose buffers count against the free memory) from the device memory.
+struct EvalPlan {
+  bool vit, postr;        // the results asked for
+  bool ratio;             // segment ratios apply: asked for and present in the batch
+  bool coop;              // N < 64: the one-workgroup kernels; else the 64 <= N <= 128 paths (tehmm_wide.hip.h)
+  int SPL;                // 64 <= N <= 128 sequential kernels: 1 up to 64 states, else 2
+  int CS;                 // chunk length of the chunk-parallel passes (0: none)
+  // chunk-parallel exact Viterbi: N < 64, at least two chunks; segment ratios only in the lane = item form (finite
+  // self-transitions, NP <= TEHMM_RATIO_LANE_MAX, the lane Viterbi pass), otherwise the sequential kernels
+  bool vspec;
+  bool fspec;             // chunk-parallel forward / backward: N < 64, at least two chunks
+  bool fused_fb;          // the fused posterior passes (tehmm_fused.hip.h): knob, the model's tables, K <= 78
+  // item length of the lane = item passes (0: none).  Their item-interleaved buffers (8 * NP bytes per position each:
+  // alpha' -- plus, without the fused passes, beta' and the linear emission rows --, the fp64 log rows of the exact
+  // Viterbi pass; 4 * NP for the float rows of P0) must fit next to the results; otherwise the lane passes do without
+  // the fp64 log rows (sticky: b->lw.no_vlane), and failing that the [T][N] speculative passes run
+  int LS;
+  bool vlane;             // the exact Viterbi pass as a lane = item pass (knob, the fp64 log rows fit)
+  bool flane;             // forward / backward as lane = item passes
+  bool glane;             // P0 (binade placement) as a packed-float lane pass; knob: the fp64 lane = state pass
+  bool emis_gain;         // emission rows and P0 in one pass, unless the round-1 posterior pipeline wants linear rows
+  // binade placement on the device (tehmm_place.hip.h; knob: the host path of rounds 1..3): everything the quantised
+  // pass needs besides the gains is put on the stream BEFORE the gain pass
+  bool dev_place;
+  int WuV;                // Viterbi warm-up of the lane passes: 32 (a multiple of 32), at most LS
+  // Order of the posterior against the Viterbi pipeline (knob, else by size): 0 none; 1 behind the Viterbi passes;
+  // 3 (fused lane passes) the forward half from the start, beside the emission-row kernel and the binade placement,
+  // the quantised pass behind the forward pass, the backward half behind it, next to the exact chain.
+  // Round 4 (ms per first evaluation, modes 0 / 1 / 3; 35 states, bench geometry): 10 Mb 17.1 / 14.9 / 15.3, 20 Mb
+  // 22.5 / 20.1 / 20.4, 30 Mb 25.8 / 27.4 / 25.3, 50 Mb 36.3 / 40.7 / 37.2, 70 Mb 51.6 / 55.4 / 48.1, 100 Mb 65.2 /
+  // 70.5 / 65.1; one 10 Mb interval 16.7 / 15.9 / 16.8: mode 3 from 25 Mb up, mode 1 below and where one chain
+  // dominates.
+  int defer_mode;
+  bool defer_post;        // both results, chunk-parallel Viterbi, mode 1 or 3: the posterior waits for its passes
+  bool split_post;        // mode 3 with the lane Viterbi and the fused lane posterior: its two halves apart
+  bool wide_defer;        // 64 <= N <= 128, both results, mode != 0: the posterior goes in at the Viterbi enqueue
+};
+
+static EvalPlan plan_eval(const tehmm_model *m, const tehmm_batch *b, int flags, const EvalKnobs &kn) {
+  EvalPlan p{};
+  p.vit = flags & TEHMM_EVAL_VITERBI;
+  p.postr = flags & TEHMM_EVAL_POSTERIOR;
+  p.ratio = (flags & TEHMM_EVAL_USE_RATIOS) && b->has_ratios;
+  p.coop = m->N < 64;
+  p.SPL = m->N <= 64 ? 1 : 2;
+  p.CS = kn.spec_chunk;
+  const bool spec_ok = p.coop && p.CS > 0 && m->NP <= 64 && b->total >= 2 * (int64_t)p.CS;
+  p.vspec = p.vit && spec_ok && (!p.ratio || (ratio_lane_ok(m) && m->NP <= TEHMM_RATIO_LANE_MAX));
+  p.fspec = p.postr && spec_ok;
+  p.fused_fb = kn.fused && m->ptab.p != nullptr && m->K <= 78;        // (96 record entries incl. padding)
+  p.LS = (p.vspec || p.fspec) ? lane_sub_size(p.CS, b->total, kn.lane_sub) : 0;
+  return p;
+}
+
+static int plan_lanes(EvalPlan &p, const tehmm_model *m, tehmm_batch *b, const EvalKnobs &kn) {
+  LaneWork &lw = b->lw;
+  if (p.LS > 0 && !lw.AL.p && !lw.AL32.p && !lw.B.p && !lw.B32.p) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(dev_mem_info(&free_b, &total_b));
+    const double per = (double)b->total * m->NP * 8.0;
+    const double fb_units = p.fspec ? (p.fused_fb ? 0.7 : 3.2) : 0.0, p0_units = (p.vspec && !p.fused_fb) ? 0.5 : 0.0;
+    lw.no_vlane = per * (fb_units + p0_units + 1.0) > 0.85 * (double)free_b;
+    if (per * (fb_units + p0_units) > 0.85 * (double)free_b) p.LS = 0;
+  }
+  bool want_vlane = kn.lane_vit;
+  if (p.LS > 0 && want_vlane && !lw.no_vlane && !lw.B.p && (lw.AL.p || lw.AL32.p || lw.B32.p)) {
+    // workspaces of an earlier call exist already: the fp64 (+ float) log rows must still fit
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(dev_mem_info(&free_b, &total_b));
+    if ((double)b->total * m->NP * 8.0 * 1.6 > 0.85 * (double)free_b) lw.no_vlane = true;
+  }
+  if (lw.no_vlane) want_vlane = false;
+  if (p.ratio && p.vspec && !(p.LS > 0 && want_vlane && (p.fused_fb || !(p.fspec && p.LS > 0)))) {
+    p.vspec = false;                                  // no lane passes for this call: sequential Viterbi with ratios
+    if (!p.fspec) p.LS = 0;
+  }
+  p.vlane = p.vspec && p.LS > 0 && want_vlane;
+  p.flane = p.fspec && p.LS > 0;
+  p.glane = p.vspec && p.LS > 0 && (p.vlane || kn.lane_p0);
+  p.emis_gain = p.glane && !(p.flane && !p.fused_fb);
+  p.dev_place = kn.device_place && p.vlane && p.emis_gain;
+  p.WuV = std::min(p.LS, 32);
+  int64_t longest = 0;
+  for (int i = 0; i < b->n; ++i) longest = std::max<int64_t>(longest, b->h_len[(size_t)i]);
+  const bool big = b->total >= (int64_t)25000000 && 4 * longest <= b->total;
+  p.defer_mode = kn.defer >= 0 ? kn.defer : (big ? 3 : 1);
+  p.defer_post = p.vit && p.postr && p.vspec && (p.defer_mode == 1 || p.defer_mode == 3);
+  p.split_post = p.defer_post && p.defer_mode == 3 && p.flane && p.fused_fb && p.vlane;
+  p.wide_defer = p.vit && p.postr && !p.vspec && !p.coop && p.defer_mode != 0;
+  return TEHMM_OK;
+}
+
+// What the stages of one call share.
+struct EvalCtx {
+  tehmm_model *m;
+  tehmm_batch *b;
+  const EvalPlan &p;
+  const EvalKnobs &kn;
+  IntervalTab iv;
+  EmisTab em, emg;             // emission tables; emg without the LDS copies
+  VitChunks vc;                // chunk tables of the chunk-parallel Viterbi (vspec)
+  int WuF;                     // forward / backward warm-up of the lane passes
+  bool wide_cp = false;        // the chunk-parallel posterior for 64 <= N <= 128 ran
+  bool wide_vit = false;       // ... and the chunk-parallel exact Viterbi
+  bool wide_pending = false;   // a chunk-parallel posterior attempt is in flight
+};
+
+// device placement: zeroed flags and counters, the argument structs of the quantised pass
+static int eval_place_setup(EvalCtx &c) {
+  tehmm_batch *b = c.b;
+  LaneWork &lw = b->lw;
+  SpecWork &sw = b->sw;
+  hipStream_t st = b->sV;
+  int rc = ensure_qtabs(c.m, c.p.ratio);
+  if (rc) return rc;
+  const size_t ng = (size_t)std::max(1, lw.n_groups);
+  HIPCHK(lw.wk_g.ensure(2 * ng + TEHMM_PLACE_NE));
+  HIPCHK(lw.wk_e.ensure(2 * ng + TEHMM_PLACE_NE));
+  HIPCHK(lw.wk_items.ensure((ng + TEHMM_PLACE_NE) * 64));
+  HIPCHK(lw.gclass.ensure(ng));
+  HIPCHK(lw.place.ensure(1));
+  HIPCHK(hipMemsetAsync(lw.place.p, 0, sizeof(PlaceCounts), st));
+  HIPCHK(hipMemsetAsync(lw.wk_items.p, 0xff, (ng + TEHMM_PLACE_NE) * 64 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(sw.ok.p, 0, (size_t)std::max(1, sw.n_chunks) * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(lw.vbad.p, 0, ng * 64 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(lw.vntie.p, 0, ng * 64 * sizeof(int), st));
+  return vit_lane_upload_args(b, c.vc, st);
+}
+
+// the emission-row / gain pass of the Viterbi pipeline; the plain gains go to the host unless placed on the device
+static int eval_emis_p0(EvalCtx &c) {
+  tehmm_batch *b = c.b;
+  const tehmm_model *m = c.m;
+  const EvalPlan &p = c.p;
+  LaneWork &lw = b->lw;
+  SpecWork &sw = b->sw;
+  std::vector<double> &gain = lw.hs_gain;
+  hipStream_t st = b->sV;
+  if (p.vlane || p.glane) {
+    // emission rows of every position, once, item-interleaved (log rows for Viterbi, linear for fwd/bwd)
+    if (p.emis_gain) {
+      nt_dispatch(m->NP, [&](auto nt) {
+        launch_emis_gain_lane<nt>(b, m, c.iv, c.em, p.CS, p.WuV, p.ratio, c.kn.emis_split, st);
+      });
+    } else {
+      nt_dispatch(m->NP, [&](auto nt) {
+        launch_emis_lane<nt>(b, m, c.iv, c.em, p.vlane, p.flane && !p.fused_fb, p.glane, st);
+      });
+    }
+    (void)hipEventRecord(b->ev[eV + 4], st);
+    if (p.flane) {
+      if (!p.fused_fb) {                                // (the fused passes compute their own emission rows)
+        (void)hipEventRecord(b->evX[0], st);
+        (void)hipStreamWaitEvent(b->sP, b->evX[0], 0);
+      }
+      (void)hipEventRecord(b->ev[eP + 4], b->sP);
+    }
+  }
+  if (p.vspec) {
+    // chunk-parallel exact Viterbi: P0 (plain gains) -> binades -> P2 (quantised) -> fix-up chain
+    if (p.glane) {
+      if (!p.emis_gain) nt_dispatch(m->NP, [&](auto nt) { launch_gain_lane<nt>(b, m, c.iv, p.CS, p.WuV, st); });
+      if (!p.dev_place) {
+        gain.resize((size_t)std::max(1, lw.n_groups) * 64);
+        HIPCHK(hipMemcpyAsync(gain.data(), lw.vgain.p, gain.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      }
+    } else {
+      nt_dispatch(m->NP, [&](auto nt) { launch_vit_spec<nt>(b, m, c.iv, c.emg, c.vc, false, st); });
+      gain.resize((size_t)std::max(1, sw.n_chunks));
+      HIPCHK(hipMemcpyAsync(gain.data(), sw.gain.p, gain.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+  }
+  return TEHMM_OK;
+}
+
+// emission rows (linear domain) for the round-1 lane posterior passes when no Viterbi lane pass made them
+static void eval_emission(EvalCtx &c) {
+  const EvalPlan &p = c.p;
+  if (!(p.flane && !p.fused_fb && !p.vlane && !p.glane)) return;
+  tehmm_batch *b = c.b;
+  hipStream_t st = b->sP;
+  nt_dispatch(c.m->NP, [&](auto nt) { launch_emis_lane<nt>(b, c.m, c.iv, c.em, false, true, false, st); });
+  (void)hipEventRecord(b->ev[eP + 4], st);
+}
+
+// half (fused passes only): 1 = the forward half now, 2 = the backward half; 0 = everything
+static int eval_posterior(EvalCtx &c, int half) {
+  tehmm_batch *b = c.b;
+  const tehmm_model *m = c.m;
+  const EvalPlan &p = c.p;
+  const IntervalTab &iv = c.iv;
+  LaneWork &lw = b->lw;
+  SpecWork &sw = b->sw;
+  hipStream_t st = b->sP;
+  int rc = TEHMM_OK;
+  if (half != 2) (void)hipEventRecord(b->ev[10], st);            // start of the passes (behind any deferral wait)
+  else (void)hipEventRecord(b->ev[11], st);                      // ... of the backward half
+  if (p.flane) {
+    // lane = item passes (forward, backward, links), then the two sequential chains on the
+    // item-interleaved rows, then the transposing combine
+    FbChunks fc{};
+    fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = p.CS;
+    fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
+    fc.link_f = lw.link_f.p; fc.glog_f = lw.glog_f.p; fc.link_b = lw.link_b.p; fc.runend_f = lw.runend_f.p;
+    fc.pre_f = lw.cpre_f.p; fc.runstart_b = lw.runstart_b.p;
+    if (half != 2) {
+      (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
+      (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
+    }
+    if (p.fused_fb) {
+      nt_dispatch(m->NP, [&](auto nt) {
+        rc = launch_fused_fb<nt>(b, m, iv, c.em, fc, c.WuF, st, b->ev[eP + 3], b->ev[eP + 1], false, half,
+                                 half == 1 ? b->evX[1] : nullptr);
+      });
+      if (rc) return rc;
+      if (half == 1) return TEHMM_OK;
+    } else {
+      nt_dispatch(m->NP, [&](auto nt) { launch_fb_lane<nt>(b, m, iv, c.em, fc, c.WuF, st, b->ev[eP + 3]); });
+      (void)hipEventRecord(b->ev[eP + 1], st);
+      nt_dispatch(m->NP, [&](auto nt) { launch_combine_lane<nt>(b, m, iv, st); });
+    }
+    hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N,
+                       b->post.p, b->fwd_lp.p);
+  } else if (p.fspec) {
+    // chunk-parallel forward / backward: speculative rows from uniform starts, then the two
+    // sequential chains (forward on this stream, backward on its own) with verified jumps
+    rc = ensure_beta(b, m);
+    if (rc) return rc;
+    FbChunks fc{};
+    fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = p.CS;
+    fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
+    (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
+    (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
+    nt_dispatch(m->NP, [&](auto nt) { launch_fb_spec<nt>(b, m, iv, c.emg, fc, st); });
+    (void)hipEventRecord(b->ev[eP + 3], st);
+    (void)hipStreamWaitEvent(b->sB, b->ev[eP + 3], 0);
+    nt_dispatch(m->NP, [&](auto nt) { launch_fb_fix<nt>(b, m, iv, c.em, fc, st, b->sB); });
+    (void)hipEventRecord(b->evX[1], b->sB);
+    (void)hipStreamWaitEvent(st, b->evX[1], 0);
+    (void)hipEventRecord(b->ev[eP + 1], st);
+    hipLaunchKernelGGL((k_combine<true>), dim3(grid_for(b->total * 16, 256, 256 * 16)), dim3(256), 0, st,
+                       b->total, m->N, b->post.p, b->beta.p);
+    hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N,
+                       b->post.p, b->fwd_lp.p);
+  } else if (p.coop) {
+    rc = ensure_beta(b, m);
+    if (rc) return rc;
+    (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
+    nt_dispatch(m->NP, [&](auto nt) { launch_fb_coop<nt>(b, m, iv, c.em, st); });
+    (void)hipEventRecord(b->ev[eP + 1], st);
+    hipLaunchKernelGGL((k_combine<true>), dim3(grid_for(b->total * 16, 256, 256 * 16)), dim3(256), 0, st,
+                       b->total, m->N, b->post.p, b->beta.p);
+    hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N, b->post.p,
+                       b->fwd_lp.p);
+  } else {
+    // 64 <= N <= 128: the chunk-parallel passes are enqueued; their verdict is read behind the Viterbi enqueue
+    // (eval_finish_wide), so the two pipelines share the GPU
+    rc = posterior_wide_cp(b, m, iv, c.em, st, b->ev[eP + 1], &c.wide_pending,
+                           c.wide_vit ? (const double *)b->ww.BL.p : nullptr);
+    if (rc) return rc;
+    if (!c.wide_pending) {
+      if (p.SPL == 1) launch_posterior<1>(b, m, iv, c.em, st, b->ev[eP + 1]);
+      else launch_posterior<2>(b, m, iv, c.em, st, b->ev[eP + 1]);
+    }
+  }
+  (void)hipEventRecord(b->ev[eP + 2], st);
+  return TEHMM_OK;
+}
+
+static int eval_finish_wide(EvalCtx &c) {
+  if (!c.wide_pending) return TEHMM_OK;
+  c.wide_pending = false;
+  tehmm_batch *b = c.b;
+  hipStream_t st = b->sP;
+  bool wide_done = false;
+  int rc = posterior_wide_finish(b, c.m, c.iv, st, b->ev[eP + 1], &wide_done);
+  if (rc) return rc;
+  c.wide_cp = wide_done;
+  if (!wide_done) {
+    if (c.p.SPL == 1) launch_posterior<1>(b, c.m, c.iv, c.em, st, b->ev[eP + 1]);
+    else launch_posterior<2>(b, c.m, c.iv, c.em, st, b->ev[eP + 1]);
+  }
+  (void)hipEventRecord(b->ev[eP + 2], st);
+  return TEHMM_OK;
+}
+
+// item gains of a lane P0 pass -> chunk gains (chunks the lanes did not run: see below)
+static void chunk_gains(const EvalCtx &c, std::vector<double> &cgain) {
+  const tehmm_batch *b = c.b;
+  const SpecWork &sw = b->sw;
+  const LaneWork &lw = b->lw;
+  const std::vector<double> &gain = lw.hs_gain;
+  const int CS = c.p.CS, LS = c.p.LS;
+  cgain.assign((size_t)std::max(1, sw.n_chunks), 0.0);
+  const int SUB = CS / LS;
+  for (int ch = 0; ch < sw.n_chunks; ++ch) {
+    const int id = sw.h_iv[(size_t)ch];
+    const int64_t it0 = lw.h_first_item(id) + sw.h_t0[(size_t)ch] / LS;
+    double gsum = 0.0;
+    const bool full = sw.h_t0[(size_t)ch] + CS <= b->h_len[id];
+    if (!full || ch == sw.h_first[id]) gsum = std::nan("");
+    else for (int k = 0; k < SUB; ++k) gsum += gain[(size_t)(it0 + k)];
+    cgain[(size_t)ch] = gsum;
+  }
+  // chunks the lanes did not run carry NaN; the prefix sums of spec_assign_binades still need a
+  // number for them: use the mean gain per position of the interval's speculated chunks
+  for (int i = 0; i < b->n; ++i) {
+    double sum = 0.0;
+    int cnt = 0;
+    for (int64_t ch = sw.h_first[i]; ch < sw.h_first[i + 1]; ++ch)
+      if (cgain[(size_t)ch] == cgain[(size_t)ch]) { sum += cgain[(size_t)ch]; ++cnt; }
+    const double mean = cnt ? sum / cnt : std::nan("");
+    for (int64_t ch = sw.h_first[i]; ch < sw.h_first[i + 1]; ++ch)
+      if (!(cgain[(size_t)ch] == cgain[(size_t)ch])) {
+        const int64_t clen = std::min<int64_t>(CS, b->h_len[i] - sw.h_t0[(size_t)ch]);
+        cgain[(size_t)ch] = (ch == sw.h_first[i] || clen < CS) ? mean * (double)clen / (double)CS : std::nan("");
+      }
+  }
+}
+
+// Binade placement on the host (waits for the gain pass): item gains -> chunk gains -> binades; the quantised tables
+// of the binades in use and one P2 wave per (group, binade) pair, uploaded on the Viterbi stream.
+static int host_place(EvalCtx &c, int *n_work, int *emin_out) {
+  tehmm_batch *b = c.b;
+  const tehmm_model *m = c.m;
+  const bool ratio = c.p.ratio;
+  const int CS = c.p.CS;
+  LaneWork &lw = b->lw;
+  SpecWork &sw = b->sw;
+  hipStream_t st = b->sV;
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<double> &cgain = lw.hs_cgain;
+  chunk_gains(c, cgain);
+  std::vector<int> &he = lw.hs_e;
+  spec_assign_binades(b, cgain, he);
+  // quantised tables of the binades in use
+  int emin = INT_MAX, emax = INT_MIN;
+  for (int ch = 0; ch < sw.n_chunks; ++ch)
+    if (he[(size_t)ch] != TEHMM_SPEC_NONE) { emin = std::min(emin, he[(size_t)ch]); emax = std::max(emax, he[(size_t)ch]); }
+  std::vector<int> &wk_g = lw.hs_wkg, &wk_e = lw.hs_wke;
+  wk_g.clear();
+  wk_e.clear();
+  if (emin <= emax) {
+    const size_t tsz = quantised_table_size(m, ratio);
+    std::vector<double> &qt = lw.hs_qt;
+    qt.assign((size_t)(emax - emin + 1) * tsz + 64, 0.0);      // (+ one block of padding: k_vit_lane3's prefetch)
+    std::vector<char> eok((size_t)(emax - emin + 1), 1);
+    for (int e = emin; e <= emax; ++e)
+      eok[(size_t)(e - emin)] = ratio ? quantised_table_ratio(m, e, qt.data() + (size_t)(e - emin) * tsz)
+                                      : quantised_table(m, e, qt.data() + (size_t)(e - emin) * tsz);
+    for (int ch = 0; ch < sw.n_chunks; ++ch)
+      if (he[(size_t)ch] != TEHMM_SPEC_NONE && !eok[(size_t)(he[(size_t)ch] - emin)]) he[(size_t)ch] = TEHMM_SPEC_NONE;
+    HIPCHK(lw.qtabs.fill_async(qt.data(), qt.size(), st));
+    // a group whose speculated items share one binade is one work unit; the items of the others (interval
+    // heads, binade crossings) are pooled per binade and dealt out 64 to a wave
+    std::vector<std::vector<int>> pool((size_t)(emax - emin + 1));
+    for (int g = 0; g < lw.n_groups; ++g) {
+      int e1 = TEHMM_SPEC_NONE;
+      bool mixed = false;
+      const int nl = std::min(64, lw.n_items - g * 64);
+      for (int ln = 0; ln < nl; ++ln) {
+        const size_t item = (size_t)g * 64 + ln;
+        const int e = he[(size_t)(sw.h_first[lw.h_iv[item]] + lw.h_t0[item] / CS)];
+        if (e == TEHMM_SPEC_NONE) continue;
+        if (e1 == TEHMM_SPEC_NONE) e1 = e;
+        else if (e != e1) mixed = true;
+      }
+      if (e1 == TEHMM_SPEC_NONE) continue;
+      if (!mixed) { wk_g.push_back(g); wk_e.push_back(e1); continue; }
+      for (int ln = 0; ln < nl; ++ln) {
+        const size_t item = (size_t)g * 64 + ln;
+        const int e = he[(size_t)(sw.h_first[lw.h_iv[item]] + lw.h_t0[item] / CS)];
+        if (e != TEHMM_SPEC_NONE) pool[(size_t)(e - emin)].push_back((int)item);
+      }
+    }
+    std::vector<int> &wki = lw.hs_wki;
+    wki.clear();
+    for (int e = emin; e <= emax; ++e) {
+      const std::vector<int> &pl = pool[(size_t)(e - emin)];
+      for (size_t i0 = 0; i0 < pl.size(); i0 += 64) {
+        const int slot = (int)(wki.size() / 64);
+        for (size_t i = 0; i < 64; ++i) wki.push_back(i0 + i < pl.size() ? pl[i0 + i] : -1);
+        wk_g.push_back(-(1 + slot));
+        wk_e.push_back(e);
+      }
+    }
+    if (!wki.empty()) HIPCHK(lw.wk_items.fill_async(wki.data(), wki.size(), st));
+  }
+  {
+    // waves of one binade next to each other: they share one quantised table in the scalar cache
+    std::vector<int> ord(wk_g.size());
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return wk_e[(size_t)x] < wk_e[(size_t)y]; });
+    std::vector<int> g2(ord.size()), e2(ord.size());
+    for (size_t i = 0; i < ord.size(); ++i) { g2[i] = wk_g[(size_t)ord[i]]; e2[i] = wk_e[(size_t)ord[i]]; }
+    wk_g.swap(g2);
+    wk_e.swap(e2);
+  }
+  *n_work = (int)wk_g.size();
+  *emin_out = emin;
+  if (*n_work > 0) {
+    HIPCHK(lw.wk_g.fill_async(wk_g.data(), wk_g.size(), st));
+    HIPCHK(lw.wk_e.fill_async(wk_e.data(), wk_e.size(), st));
+  }
+  HIPCHK(hipMemcpyAsync(sw.e.p, he.data(), he.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sw.gain.p, cgain.data(), cgain.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(sw.ok.p, 0, he.size() * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(lw.vbad.p, 0, (size_t)std::max(1, lw.n_groups) * 64 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(lw.vntie.p, 0, (size_t)std::max(1, lw.n_groups) * 64 * sizeof(int), st));
+  return vit_lane_upload_args(b, c.vc, st);
+}
+
+// the rest of the Viterbi pipeline (behind the emission / gain pass): binades, the quantised pass, the exact chain (the
+// deferred posterior goes in between), the traceback
+static int eval_viterbi(EvalCtx &c) {
+  tehmm_batch *b = c.b;
+  const tehmm_model *m = c.m;
+  const EvalPlan &p = c.p;
+  const IntervalTab &iv = c.iv;
+  LaneWork &lw = b->lw;
+  SpecWork &sw = b->sw;
+  hipStream_t st = b->sV;
+  int rc = TEHMM_OK;
+  if (p.vlane) {
+    const bool soft = c.kn.soft_ties;
+    if (p.dev_place) {
+      int n_work_max = 0;
+      rc = launch_vit_place(b, m, iv, p.CS, p.ratio, st, &n_work_max);
+      if (rc) return rc;
+      if (p.split_post) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
+      nt_dispatch(m->NP, [&](auto nt) {
+        launch_vit_lane<nt>(b, m, iv, c.vc, p.ratio, soft, p.WuV, n_work_max, (const double *)m->qall[p.ratio ? 1 : 0].p,
+                            TEHMM_SPEC_MIN_E, (const int *)&lw.place.p->n_work, st);
+      });
+    } else {
+      int n_work = 0, emin = 0;
+      rc = host_place(c, &n_work, &emin);
+      if (rc) return rc;
+      if (p.split_post) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
+      nt_dispatch(m->NP, [&](auto nt) {
+        launch_vit_lane<nt>(b, m, iv, c.vc, p.ratio, soft, p.WuV, n_work, (const double *)lw.qtabs.p, emin,
+                            (const int *)nullptr, st);
+      });
+    }
+    nt_dispatch(m->NP, [&](auto nt) { launch_vit_stitch<nt>(b, m, iv, c.vc, st); });
+    (void)hipEventRecord(b->ev[eV + 3], st);
+    if (p.defer_post) {
+      (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
+      rc = eval_posterior(c, p.split_post ? 2 : 0);
+      if (rc) return rc;
+    }
+    nt_dispatch(m->NP, [&](auto nt) { launch_vit_fix<nt>(b, m, iv, c.em, c.vc, true, p.ratio, st); });
+  } else if (p.vspec) {
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int> &he = lw.hs_e;
+    if (p.glane) {
+      std::vector<double> &cgain = lw.hs_cgain;
+      chunk_gains(c, cgain);
+      spec_assign_binades(b, cgain, he);
+      HIPCHK(hipMemcpyAsync(sw.gain.p, cgain.data(), cgain.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    } else {
+      spec_assign_binades(b, lw.hs_gain, he);
+    }
+    HIPCHK(hipMemcpyAsync(sw.e.p, he.data(), he.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(sw.ok.p, 0, he.size() * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
+    nt_dispatch(m->NP, [&](auto nt) { launch_vit_spec<nt>(b, m, iv, c.emg, c.vc, true, st); });
+    (void)hipEventRecord(b->ev[eV + 3], st);
+    if (p.defer_post) {
+      (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
+      rc = eval_posterior(c, 0);
+      if (rc) return rc;
+    }
+    nt_dispatch(m->NP, [&](auto nt) { launch_vit_fix<nt>(b, m, iv, c.em, c.vc, false, false, st); });
+  } else if (p.coop) {
+    nt_dispatch(m->NP, [&](auto nt) { launch_vit_coop<nt>(b, m, iv, c.em, p.ratio, st); });
+  } else {
+    rc = viterbi_wide_cp(b, m, iv, c.em, p.ratio, st, b->ev[eV + 3], &c.wide_vit);
+    if (rc) return rc;
+    if (!c.wide_vit) {
+      if (p.SPL == 1) launch_viterbi<1>(b, m, iv, c.em, p.ratio, st);
+      else launch_viterbi<2>(b, m, iv, c.em, p.ratio, st);
+    }
+    if (p.wide_defer) {
+      // the posterior passes go behind the quantised Viterbi pass, next to the exact chain (few CUs, latency-bound)
+      if (c.wide_vit) (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
+      rc = eval_posterior(c, 0);
+      if (rc) return rc;
+    }
+  }
+  (void)hipEventRecord(b->ev[eV + 1], st);
+  allow_lds(k_tb_compose<uint8_t>, 4 * TEHMM_TB_STAGE);
+  allow_lds(k_tb_fill<uint8_t>, 4 * TEHMM_TB_STAGE);
+  if (b->n_chunks > 0)
+    hipLaunchKernelGGL(k_tb_compose<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv, b->d_chunk_iv.p,
+                       b->d_chunk0.p, b->n_chunks, m->N, m->NP, b->TBW, b->tb.p, b->G.p);
+  {
+    // long intervals: two-level scan (tiles of 64 chunk maps composed in parallel)
+    int64_t maxc = 0;
+    for (int i = 0; i < b->n; ++i) maxc = std::max<int64_t>(maxc, b->h_chunk0[(size_t)i + 1] - b->h_chunk0[(size_t)i]);
+    const int maxt = (int)((maxc + 63) / 64);
+    if (maxt > 8 && maxt <= 65535) {          // (grid.y limit: longer intervals keep the one-level scan)
+      const size_t ntile = (size_t)b->n_chunks / 64 + (size_t)b->n + 2;
+      HIPCHK(b->Gg.ensure(ntile * m->NP));
+      HIPCHK(b->tstate.ensure(ntile));
+      hipLaunchKernelGGL(k_tb_group<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->G.p,
+                         b->Gg.p);
+      hipLaunchKernelGGL(k_tb_scan_top<uint8_t>, dim3(b->n), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->Gg.p,
+                         (const int *)b->last_state.p, b->tstate.p, b->paths.p);
+      hipLaunchKernelGGL(k_tb_scan_tiles<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
+                         (const uint8_t *)b->G.p, (const uint8_t *)b->tstate.p, b->bstate.p);
+    } else {
+      hipLaunchKernelGGL(k_tb_scan<uint8_t>, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
+                         b->G.p, b->last_state.p, b->bstate.p, b->paths.p);
+    }
+  }
+  if (b->n_chunks > 0)
+    hipLaunchKernelGGL(k_tb_fill<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv,
+                       b->n_chunks, b->d_chunk_iv.p, b->d_chunk0.p, b->TBW, b->tb.p, b->bstate.p,
+                       b->paths.p);
+  (void)hipEventRecord(b->ev[eV + 2], st);
+  return TEHMM_OK;
+}
+
+// The stage timings of a call: names and event pairs, Viterbi stages first.
+static void eval_timings(const EvalPlan &p, tehmm_batch *b) {
+  auto add = [&](const char *name, int e0, int e1) {
+    b->tnames.push_back(name);
+    b->tpairs.push_back({e0, e1});
+  };
+  if (p.vit) {
+    if (p.vlane || p.glane) {
+      add("emission_rows", eV, eV + 4);
+      add("viterbi_speculate", eV + 4, eV + 3);
+      add("viterbi", eV + 3, eV + 1);
+    } else if (p.vspec) {
+      add("viterbi_speculate", eV, eV + 3);
+      add("viterbi", eV + 3, eV + 1);
+    } else {
+      add("viterbi", eV, eV + 1);
+    }
+    add("traceback", eV + 1, eV + 2);
+  }
+  if (p.postr) {
+    if (p.flane && p.fused_fb) {
+      add("forward_pass", 10, eP + 3);                                   // lane pass + links + exact forward chain
+      add("backward_posterior_pass", p.split_post ? 11 : eP + 3, eP + 1); // lane pass incl. the posterior rows + links
+    } else if (p.flane) {
+      if (!p.vlane && !p.glane) add("emission_rows", eP, eP + 4);
+      add("forward_backward_speculate", 10, eP + 3);
+      add("forward_backward", eP + 3, eP + 1);
+    } else if (p.fspec) {
+      add("forward_backward_speculate", eP, eP + 3);
+      add("forward_backward", eP + 3, eP + 1);
+    } else {
+      add(p.coop ? "forward_backward" : "forward", eP, eP + 1);
+    }
+    add(p.flane && p.fused_fb ? "backward_chain" : (p.coop ? "posterior_combine" : "backward_posterior"), eP + 1, eP + 2);
+  }
+}
+
+// counters (not times) behind the timings, once both streams are through
+static int eval_counters(const EvalCtx &c) {
+  tehmm_batch *b = c.b;
+  auto add = [&](const char *name, double v) {
+    b->tnames.push_back(name);
+    b->tms.push_back(v);
+  };
+  if (c.p.fspec) {
+    int st[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(st, b->sw.stats.p + 2, sizeof(st), hipMemcpyDeviceToHost));
+    add("count:forward_exact_blocks", st[0]);
+    add("count:forward_chunk_jumps", st[1]);
+    add("count:backward_exact_blocks", st[2]);
+    add("count:backward_chunk_jumps", st[3]);
+  }
+  if (c.wide_cp) add("count:wide_chunk_parallel_warmup", b->ww.wu_ok);
+  if (c.wide_vit) {
+    int st2[2] = {0, 0};
+    HIPCHK(hipMemcpy(st2, b->sw.stats.p, sizeof(st2), hipMemcpyDeviceToHost));
+    add("count:viterbi_exact_blocks", st2[0]);
+    add("count:viterbi_chunk_jumps", st2[1]);
+  }
+  if (c.p.vspec) {
+    // 64-position blocks the exact chain ran / chunks it could jump over
+    int st[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(st, b->sw.stats.p, sizeof(st), hipMemcpyDeviceToHost));
+#ifdef TEHMM_CHAIN_PROF
+    {
+      int pr[4];
+      HIPCHK(hipMemcpy(pr, b->sw.stats.p + 8, sizeof(pr), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemset(b->sw.stats.p + 8, 0, sizeof(pr)));
+      std::fprintf(stderr, "[chain prof] summed over intervals, ms: prologue %.2f steps %.2f barrier %.2f\n", pr[0] * 1e-4,
+                   pr[1] * 1e-4, pr[2] * 1e-4);
+    }
+#endif
+    add("count:viterbi_exact_blocks", st[0]);
+    add("count:viterbi_chunk_jumps", st[1]);
+  }
+  return TEHMM_OK;
+}
+
 int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *viterbi_logprob,
                      double *forward_logprob) {
   if (!m || !b) return fail(TEHMM_ERR_ARG, "tehmm_eval_batch: NULL handle");
@@ -2743,699 +3323,87 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
 #endif
   int rc = ensure_workspace(b, m, flags);
   if (rc) return rc;
-  const bool ratio = (flags & TEHMM_EVAL_USE_RATIOS) && b->has_ratios;
-  IntervalTab iv;
-  EmisTab em;
-  fill_tabs(m, b, iv, em, false);   // decode / score_samples never apply ratios to emissions
-  const int SPL = m->N <= 64 ? 1 : 2;
-  const bool coop = m->N < 64;
-  // Enqueue order: Viterbi speculation pass 0 -> the whole posterior pipeline (async on its own
-  // streams) -> host binade assignment (needs pass 0) -> rest of the Viterbi pipeline.
-  const int CS = spec_chunk_size();
-  const bool spec_ok = coop && CS > 0 && m->NP <= 64 && b->total >= 2 * (int64_t)CS;
-  const bool vit = flags & TEHMM_EVAL_VITERBI, postr = flags & TEHMM_EVAL_POSTERIOR;
-  // segment ratios: the chunk-parallel Viterbi path takes them in its lane = item form only (finite
-  // self-transitions, NP <= 36, the fused P0 pass); otherwise the sequential kernels
-  bool vspec = vit && spec_ok && (!ratio || (ratio_lane_ok(m) && m->NP <= TEHMM_RATIO_LANE_MAX));
-  const bool fspec = postr && spec_ok;
-  if (vspec || fspec) {
-    rc = spec_prepare(b, m, CS);
+  const EvalKnobs kn = read_eval_knobs();
+  EvalPlan p = plan_eval(m, b, flags, kn);
+  if (p.vspec || p.fspec) {
+    rc = spec_prepare(b, m, p.CS);
     if (rc) return rc;
   }
-  SpecWork &sw = b->sw;
-  LaneWork &lw = b->lw;
-  const EmisTab emg = without_lds_tables(em);
-  const int eV = 0, eP = 5;
-  // lane = item geometry: the VALU lane passes (exact Viterbi, P0) hold 4 * NP VGPRs of state and stop at 36
-  // padded states; the fused matrix-core forward / backward passes go up to 64
-  const bool lane_vit_ok = m->NP <= 64;
-  int LS = ((vspec && lane_vit_ok) || fspec) ? lane_sub_size(CS, b->total) : 0;
-  // The lane = item Viterbi passes (TEHMM_LANE_VIT, default on) additionally need the fp64 log rows.
-  const char *lvs = std::getenv("TEHMM_LANE_VIT");
-  bool want_vlane = !(lvs && std::atoi(lvs) == 0);
-  // TEHMM_FUSED=0 selects the round-1 posterior pipeline (emission rows, alpha' and beta' through HBM,
-  // separate combine); default: the fused passes of tehmm_fused.hip.h
-  const char *fus = std::getenv("TEHMM_FUSED");
-  const bool fused_fb = !(fus && std::atoi(fus) == 0) && m->ptab.p != nullptr && m->K <= 78;   // (96 record entries incl. padding)
-  if (LS > 0 && !b->lw.AL.p && !b->lw.AL32.p && !b->lw.B.p && !b->lw.B32.p) {
-    // the item-interleaved buffers (8 * NP bytes per position each: alpha' -- plus, without the fused
-    // passes, beta' and the linear emission rows --, the fp64 log rows of the exact Viterbi pass; 4 * NP
-    // for the float rows of P0) must fit next to the results; otherwise do without the fp64 log rows, and
-    // failing that stay with the [T][N] speculative passes
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(dev_mem_info(&free_b, &total_b));
-    const double per = (double)b->total * m->NP * 8.0;
-    const double fb_units = fspec ? (fused_fb ? 0.7 : 3.2) : 0.0, p0_units = (vspec && !fused_fb) ? 0.5 : 0.0;
-    b->lw.no_vlane = per * (fb_units + p0_units + 1.0) > 0.85 * (double)free_b;
-    if (per * (fb_units + p0_units) > 0.85 * (double)free_b) LS = 0;
-  }
-  if (LS > 0 && want_vlane && !b->lw.no_vlane && !b->lw.B.p && (b->lw.AL.p || b->lw.AL32.p || b->lw.B32.p)) {
-    // workspaces of an earlier call exist already: the fp64 (+ float) log rows must still fit
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(dev_mem_info(&free_b, &total_b));
-    if ((double)b->total * m->NP * 8.0 * 1.6 > 0.85 * (double)free_b) b->lw.no_vlane = true;
-  }
-  if (b->lw.no_vlane) want_vlane = false;
-  if (ratio && vspec && !(LS > 0 && want_vlane && (fused_fb || !(fspec && LS > 0)))) {
-    vspec = false;                                    // no lane passes for this call: sequential Viterbi with ratios
-    if (!fspec) LS = 0;
-  }
-  const bool vlane = vspec && LS > 0 && want_vlane && lane_vit_ok, flane = fspec && LS > 0;
-  // P0 (binade placement) as a packed-float lane pass over float emission rows; TEHMM_LANE_P0=0 keeps
-  // the fp64 lane = state pass
-  const char *lp0 = std::getenv("TEHMM_LANE_P0");
-  const bool glane = vspec && LS > 0 && lane_vit_ok && (vlane || !(lp0 && std::atoi(lp0) == 0));
-  int WuF = std::min(std::max(LS, 1), 64);                                   // forward / backward warm-up (set below)
-  const char *wvs = std::getenv("TEHMM_LANE_WARMUP_VIT");
-  const int WuV = std::min(LS, std::max(32, ((wvs ? std::atoi(wvs) : 32) + 31) & ~31));   // Viterbi warm-up (multiple of 32)
-  VitChunks vc;
-  std::vector<double> &gain = lw.hs_gain;
-  if (vit) (void)hipEventRecord(b->ev[eV], b->sV);
-  // emission rows and P0 in one pass (no float copy of the rows) unless the round-1 posterior pipeline, which
-  // takes its linear rows from the row kernel, is selected
-  const bool emis_gain = glane && !(flane && !fused_fb);
-  if (vlane || flane || glane) {
-    rc = lane_prepare(b, m, CS, LS, flane, vlane, glane, fused_fb, !emis_gain);
+  rc = plan_lanes(p, m, b, kn);
+  if (rc) return rc;
+  EvalCtx c{m, b, p, kn};
+  fill_tabs(m, b, c.iv, c.em, false);   // decode / score_samples never apply ratios to emissions
+  c.emg = without_lds_tables(c.em);
+  c.WuF = std::min(std::max(p.LS, 1), 64);
+  // Enqueue order: the emission / gain pass of the Viterbi pipeline -> the posterior pipeline (async on its own
+  // streams, or the parts of it that do not wait for the Viterbi passes) -> binade placement -> the rest of the
+  // Viterbi pipeline.  The speculative passes, the emission rows, the forward / backward lane passes and the combine
+  // are throughput kernels that each fill the GPU; the fix-up chains and the traceback are latency kernels on a few
+  // CUs: a deferred posterior runs next to the Viterbi fix-up chain instead of competing with the passes that chain
+  // is waiting for.
+  if (p.vit) (void)hipEventRecord(b->ev[eV], b->sV);
+  if (p.vlane || p.flane || p.glane) {
+    rc = lane_prepare(b, m, p.CS, p.LS, p.flane, p.vlane, p.glane, p.fused_fb, !p.emis_gain);
     if (rc) return rc;
   }
-  if (flane) {
-    rc = fb_warmup(b, m, LS, iv, emg, &WuF);
+  if (p.flane) {
+    rc = fb_warmup(b, m, p.LS, c.iv, c.emg, kn, &c.WuF);
     if (rc) return rc;
   }
-  // Scheduling.  The speculative Viterbi passes, the emission rows, the forward / backward lane passes
-  // and the combine are throughput kernels that each fill the GPU; the fix-up chains and the traceback
-  // are latency kernels on a few CUs.  With both requested, the Viterbi passes go first and the
-  // posterior pipeline is released behind them (event), so that its wide kernels run next to the
-  // Viterbi fix-up chain instead of competing with the passes that chain is waiting for (its emission
-  // rows, which depend on nothing, are computed up front).
-  const char *dfs = std::getenv("TEHMM_DEFER");
-  // 0: no order, 1: behind the Viterbi passes, 2: behind the emission rows only.  Measured (ms per step, modes 1 / 2;
-  // 35 states, bench geometry): 10 Mb 15.6 / 15.9, 20 Mb 21.8 / 21.7, 30 Mb 28.3 / 26.0, 50 Mb 45.1 / 41.2, 70 Mb 60.1 /
-  // 56.3, 100 Mb 73.3 / 75.6 (mode 0: 76.0).  Below ~3 waves per SIMD the one-wave quantised pass and the emission
-  // kernel leave tails that the posterior passes fill (mode 2); on a full GPU they only take from each other and the
-  // exact chain loses its quiet partner (mode 1).
-  // Mode 3 (fused passes): the FORWARD half runs from the start, beside the emission-row kernel and the host's binade
-  // placement; the quantised pass waits for the forward pass itself and then has the GPU alone; the backward half
-  // follows it, next to the exact chain.
-  // Where ONE chain dominates (a single 10 Mb interval: 16.0 / 18.1) mode 1 keeps the posterior passes as its partner.
-  int64_t longest = 0;
-  for (int i = 0; i < b->n; ++i) longest = std::max<int64_t>(longest, b->h_len[(size_t)i]);
-  // Round 4 (three-wave quantised pass at 168 registers, binade placement on the device; tools/defer_sweep.py, ms per
-  // first evaluation, modes 0 / 1 / 2 / 3): 10 Mb 17.1 / 14.9 / 15.3 / 15.3, 20 Mb 22.5 / 20.1 / 20.5 / 20.4, 30 Mb
-  // 25.8 / 27.4 / 26.7 / 25.3, 50 Mb 36.3 / 40.7 / 37.5 / 37.2, 70 Mb 51.6 / 55.4 / 53.5 / 48.1, 100 Mb 65.2 / 70.5 /
-  // 67.7 / 65.1; one 10 Mb interval 16.7 / 15.9 / 17.2 / 16.8.  With the host out of the Viterbi pipeline the overlapped
-  // orders win from 25 Mb up: mode 3 there, mode 1 below and where one chain dominates.
-  const bool big = b->total >= (int64_t)25000000 && 4 * longest <= b->total;
-  const int defer_mode = dfs ? std::atoi(dfs) : (big ? 3 : 1);
-  const bool defer_post = vit && postr && vspec && (defer_mode == 1 || defer_mode == 3 || defer_mode == 5);
-  const bool split_post = defer_post && (defer_mode == 3 || defer_mode == 5) && flane && fused_fb && vlane;
-  if (postr) (void)hipEventRecord(b->ev[eP], b->sP);
-  // Binade placement on the device (tehmm_place.hip.h; TEHMM_DEVICE_PLACE=0: the host path of rounds 1..3): everything
-  // the quantised pass needs besides the gains -- zeroed flags, the argument structs, the tables of all binades -- is
-  // put on the stream BEFORE the gain pass, so that nothing but four small kernels separates the two passes.
-  const bool dev_place_on = !(std::getenv("TEHMM_DEVICE_PLACE") && std::atoi(std::getenv("TEHMM_DEVICE_PLACE")) == 0);
-  const bool dev_place = dev_place_on && vlane && emis_gain;
-  if (vspec) {
-    vc.iv = sw.iv.p; vc.t0 = sw.t0.p; vc.first = sw.first.p; vc.n = sw.n_chunks; vc.CS = CS;
+  if (p.postr) (void)hipEventRecord(b->ev[eP], b->sP);
+  if (p.vspec) {
+    const SpecWork &sw = b->sw;
+    VitChunks &vc = c.vc;
+    vc.iv = sw.iv.p; vc.t0 = sw.t0.p; vc.first = sw.first.p; vc.n = sw.n_chunks; vc.CS = p.CS;
     vc.e = sw.e.p; vc.gain = sw.gain.p; vc.ok = sw.ok.p; vc.wmin = sw.wmin.p; vc.rows = sw.rows.p;
     vc.ntie = sw.ntie.p; vc.ties = sw.ties.p; vc.tierows = sw.tierows.p; vc.segmin = sw.segmin.p;
     vc.offend = sw.offend.p; vc.clink = sw.clink.p; vc.clk = sw.clk.p;
     vc.rtarget = sw.rtarget.p; vc.rsel = sw.rsel.p; vc.racc = sw.racc.p; vc.rmn = sw.rmn.p;
     vc.tsoft = sw.tsoft.p; vc.tpar = sw.tpar.p;
   }
-  if (dev_place) {
-    hipStream_t st = b->sV;
-    rc = ensure_qtabs(m, ratio);
-    if (rc) return rc;
-    const size_t ng = (size_t)std::max(1, lw.n_groups);
-    HIPCHK(lw.wk_g.ensure(2 * ng + TEHMM_PLACE_NE));
-    HIPCHK(lw.wk_e.ensure(2 * ng + TEHMM_PLACE_NE));
-    HIPCHK(lw.wk_items.ensure((ng + TEHMM_PLACE_NE) * 64));
-    HIPCHK(lw.gclass.ensure(ng));
-    HIPCHK(lw.place.ensure(1));
-    HIPCHK(hipMemsetAsync(lw.place.p, 0, sizeof(PlaceCounts), st));
-    HIPCHK(hipMemsetAsync(lw.wk_items.p, 0xff, (ng + TEHMM_PLACE_NE) * 64 * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(sw.ok.p, 0, (size_t)std::max(1, sw.n_chunks) * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(lw.vbad.p, 0, ng * 64 * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(lw.vntie.p, 0, ng * 64 * sizeof(int), st));
-    rc = vit_lane_upload_args(b, vc, st);
+  if (p.dev_place) {
+    rc = eval_place_setup(c);
     if (rc) return rc;
   }
-  // the emission-row / gain pass of the Viterbi pipeline (a lambda since round 4: mode 5 enqueues it BEHIND the forward pass)
-  auto enqueue_emis_p0 = [&]() -> int {
-  if (vlane || glane) {
-      // emission rows of every position, once, item-interleaved (log rows for Viterbi, linear for fwd/bwd)
-      hipStream_t st = b->sV;
-      if (emis_gain) {
-#define CALL(NT_) launch_emis_gain_lane<NT_>(b, m, iv, em, CS, WuV, ratio, st)
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      } else {
-#define CALL(NT_) launch_emis_lane<NT_>(b, m, iv, em, vlane, flane && !fused_fb, glane, st)
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      }
-      (void)hipEventRecord(b->ev[eV + 4], st);
-      if (flane) {
-        if (!fused_fb) {                                  // (the fused passes compute their own emission rows)
-          (void)hipEventRecord(b->evX[0], st);
-          (void)hipStreamWaitEvent(b->sP, b->evX[0], 0);
-        }
-        (void)hipEventRecord(b->ev[eP + 4], b->sP);
-      }
-    }
-    if (vspec) {
-      // chunk-parallel exact Viterbi: P0 (plain gains) -> binades -> P2 (quantised) -> fix-up chain
-      hipStream_t st = b->sV;
-      if (glane) {
-        if (!emis_gain) {
-#define CALL(NT_) launch_gain_lane<NT_>(b, m, iv, CS, WuV, st)
-          TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-        }
-        if (!dev_place) {
-          gain.resize((size_t)std::max(1, lw.n_groups) * 64);
-          HIPCHK(hipMemcpyAsync(gain.data(), lw.vgain.p, gain.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-      } else {
-#define CALL(NT_) launch_vit_spec<NT_>(b, m, iv, emg, vc, false, st)
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-        gain.resize((size_t)std::max(1, sw.n_chunks));
-        HIPCHK(hipMemcpyAsync(gain.data(), sw.gain.p, gain.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
-    }
-    return TEHMM_OK;
-  };
-  // mode 5 (round 4): as mode 3, but the emission + gain pass waits for the forward KERNEL: the forward pass runs alone
-  // (12 ms instead of 17 beside the exact Viterbi chain, or 26 beside the emission kernel), then emission + gain pass,
-  // quantised pass, and the backward half beside the exact chain and the traceback
-  const bool f_first = split_post && defer_mode == 5;
-  if (!f_first) {
-    rc = enqueue_emis_p0();
-    if (rc) return rc;
-  }
-  auto enqueue_emission = [&]() {
-    if (flane && !fused_fb && !vlane && !glane) {
-      // emission rows (linear domain) for the forward / backward lane passes
-      hipStream_t st = b->sP;
-#define CALL(NT_) launch_emis_lane<NT_>(b, m, iv, em, false, true, false, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->ev[eP + 4], st);
-    }
-  };
-  bool wide_cp = false;                             // the chunk-parallel posterior for 64 <= N <= 128 ran
-  bool wide_vit = false;                            // ... and the chunk-parallel exact Viterbi
-  bool wide_pending = false;                        // a chunk-parallel posterior attempt is in flight
-  // half (fused passes only): 1 = the forward half now, 2 = the backward half; 0 = everything
-  auto enqueue_posterior = [&](int half = 0) -> int {
-    hipStream_t st = b->sP;
-    if (half != 2) (void)hipEventRecord(b->ev[10], st);            // start of the passes (behind any deferral wait)
-    else (void)hipEventRecord(b->ev[11], st);                      // ... of the backward half
-    if (flane) {
-      // lane = item passes (forward, backward, links), then the two sequential chains on the
-      // item-interleaved rows, then the transposing combine
-      FbChunks fc{};
-      fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = CS;
-      fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
-      fc.link_f = lw.link_f.p; fc.glog_f = lw.glog_f.p; fc.link_b = lw.link_b.p; fc.runend_f = lw.runend_f.p;
-      fc.pre_f = lw.cpre_f.p; fc.runstart_b = lw.runstart_b.p;
-      if (half != 2) {
-        (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
-        (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
-      }
-      if (fused_fb) {
-        int rcf = TEHMM_OK;
-#define CALL(NT_) rcf = launch_fused_fb<NT_>(b, m, iv, em, fc, WuF, st, b->ev[eP + 3], b->ev[eP + 1], false, half, half == 1 ? b->evX[1] : nullptr)
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-        if (rcf) return rcf;
-        if (half == 1) return TEHMM_OK;
-      } else {
-#define CALL(NT_) launch_fb_lane<NT_>(b, m, iv, em, fc, WuF, st, b->ev[eP + 3])
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-        (void)hipEventRecord(b->ev[eP + 1], st);
-#define CALL(NT_) launch_combine_lane<NT_>(b, m, iv, st)
-        TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      }
-      hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N,
-                         b->post.p, b->fwd_lp.p);
-    } else if (fspec) {
-      // chunk-parallel forward / backward: speculative rows from uniform starts, then the two
-      // sequential chains (forward on this stream, backward on its own) with verified jumps
-      rc = ensure_beta(b, m);
-      if (rc) return rc;
-      FbChunks fc{};
-      fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = CS;
-      fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
-      (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
-      (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
-#define CALL(NT_) launch_fb_spec<NT_>(b, m, iv, emg, fc, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->ev[eP + 3], st);
-      (void)hipStreamWaitEvent(b->sB, b->ev[eP + 3], 0);
-#define CALL(NT_) launch_fb_fix<NT_>(b, m, iv, em, fc, st, b->sB)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->evX[1], b->sB);
-      (void)hipStreamWaitEvent(st, b->evX[1], 0);
-      (void)hipEventRecord(b->ev[eP + 1], st);
-      hipLaunchKernelGGL((k_combine<true>), dim3(grid_for(b->total * 16, 256, 256 * 16)), dim3(256), 0, st,
-                         b->total, m->N, b->post.p, b->beta.p);
-      hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N,
-                         b->post.p, b->fwd_lp.p);
-    } else if (coop) {
-      rc = ensure_beta(b, m);
-      if (rc) return rc;
-      (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
-#define CALL(NT_) launch_fb_coop<NT_>(b, m, iv, em, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->ev[eP + 1], st);
-      hipLaunchKernelGGL((k_combine<true>), dim3(grid_for(b->total * 16, 256, 256 * 16)), dim3(256), 0, st,
-                         b->total, m->N, b->post.p, b->beta.p);
-      hipLaunchKernelGGL(k_poison_dead, dim3(64, std::min(b->n, 1024)), dim3(256), 0, st, iv, b->dead.p, m->N, b->post.p,
-                         b->fwd_lp.p);
-    } else {
-      // 64 <= N <= 128: the chunk-parallel passes are enqueued; their verdict is read behind the Viterbi enqueue
-      // (finish_wide_posterior), so the two pipelines share the GPU
-      rc = posterior_wide_cp(b, m, iv, em, st, b->ev[eP + 1], &wide_pending, wide_vit ? (const double *)b->ww.BL.p : nullptr);
-      if (rc) return rc;
-      if (!wide_pending) {
-        if (SPL == 1) launch_posterior<1>(b, m, iv, em, st, b->ev[eP + 1]);
-        else launch_posterior<2>(b, m, iv, em, st, b->ev[eP + 1]);
-      }
-    }
-    (void)hipEventRecord(b->ev[eP + 2], st);
-    return TEHMM_OK;
-  };
-  auto finish_wide_posterior = [&]() -> int {
-    if (!wide_pending) return TEHMM_OK;
-    wide_pending = false;
-    hipStream_t st = b->sP;
-    bool wide_done = false;
-    int rcw = posterior_wide_finish(b, m, iv, st, b->ev[eP + 1], &wide_done);
-    if (rcw) return rcw;
-    wide_cp = wide_done;
-    if (!wide_done) {
-      if (SPL == 1) launch_posterior<1>(b, m, iv, em, st, b->ev[eP + 1]);
-      else launch_posterior<2>(b, m, iv, em, st, b->ev[eP + 1]);
-    }
-    (void)hipEventRecord(b->ev[eP + 2], st);
-    return TEHMM_OK;
-  };
-  if (postr && defer_post) enqueue_emission();      // the emission rows do not wait (17 ms next to P0)
-  if (split_post) {
-    rc = enqueue_posterior(1);
-    if (rc) return rc;
-    if (f_first) {
-      (void)hipStreamWaitEvent(b->sV, b->evX[1], 0);       // the forward kernel is through
-      rc = enqueue_emis_p0();
-      if (rc) return rc;
-    }
-  } else if (postr && defer_post && flane && fused_fb) {
-    // neither do the index records of the fused passes: they only read the observations
-    int rcp = TEHMM_OK;
-    FusedOrder fo_unused;
-#define CALL(NT_) rcp = fused_prepare<NT_>(b, m, iv, WuF, b->sP, fo_unused)
-    TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    if (rcp) return rcp;
-  }
-  // 64 <= N <= 128 (tehmm_wide.hip.h), both results: the same order, arranged at the Viterbi enqueue below
-  const bool wide_defer = vit && postr && !vspec && !coop && m->N >= 64 && defer_mode != 0;
-  if (postr && !defer_post) {
-    enqueue_emission();
-    if (!wide_defer) {
-      if (defer_mode == 2 && vit && vspec && (vlane || glane)) (void)hipStreamWaitEvent(b->sP, b->ev[eV + 4], 0);
-      rc = enqueue_posterior();
-      if (rc) return rc;
-    }
-  }
-  // item gains of a lane P0 pass -> chunk gains (chunks the lanes did not run: see below)
-  auto chunk_gains = [&](std::vector<double> &cgain) {
-      cgain.assign((size_t)std::max(1, sw.n_chunks), 0.0);
-      const int SUB = CS / LS;
-      for (int c = 0; c < sw.n_chunks; ++c) {
-        const int id = sw.h_iv[(size_t)c];
-        const int64_t it0 = lw.h_first_item(id) + sw.h_t0[(size_t)c] / LS;
-        double gsum = 0.0;
-        const bool full = sw.h_t0[(size_t)c] + CS <= b->h_len[id];
-        if (!full || c == sw.h_first[id]) gsum = std::nan("");
-        else for (int k = 0; k < SUB; ++k) gsum += gain[(size_t)(it0 + k)];
-        cgain[(size_t)c] = gsum;
-      }
-      // chunks the lanes did not run carry NaN; the prefix sums of spec_assign_binades still need a
-      // number for them: use the mean gain per position of the interval's speculated chunks
-      for (int i = 0; i < b->n; ++i) {
-        double sum = 0.0;
-        int cnt = 0;
-        for (int64_t c = sw.h_first[i]; c < sw.h_first[i + 1]; ++c)
-          if (cgain[(size_t)c] == cgain[(size_t)c]) { sum += cgain[(size_t)c]; ++cnt; }
-        const double mean = cnt ? sum / cnt : std::nan("");
-        for (int64_t c = sw.h_first[i]; c < sw.h_first[i + 1]; ++c)
-          if (!(cgain[(size_t)c] == cgain[(size_t)c])) {
-            const int64_t clen = std::min<int64_t>(CS, b->h_len[i] - sw.h_t0[(size_t)c]);
-            cgain[(size_t)c] = (c == sw.h_first[i] || clen < CS) ? mean * (double)clen / (double)CS : std::nan("");
-          }
-      }
-  };
-  if (vit) {
-    hipStream_t st = b->sV;
-    if (vlane && !dev_place) {
-      HIPCHK(hipStreamSynchronize(st));
-      // item gains -> chunk gains -> binades; one P2 wave per (group, binade) pair
-      std::vector<double> &cgain = lw.hs_cgain;
-      chunk_gains(cgain);
-      std::vector<int> &he = lw.hs_e;
-      spec_assign_binades(b, cgain, he);
-      // quantised tables of the binades in use
-      int emin = INT_MAX, emax = INT_MIN;
-      for (int c = 0; c < sw.n_chunks; ++c)
-        if (he[(size_t)c] != TEHMM_SPEC_NONE) { emin = std::min(emin, he[(size_t)c]); emax = std::max(emax, he[(size_t)c]); }
-      std::vector<int> &wk_g = lw.hs_wkg, &wk_e = lw.hs_wke;
-      wk_g.clear();
-      wk_e.clear();
-      if (emin <= emax) {
-        const size_t tsz = quantised_table_size(m, ratio);
-        std::vector<double> &qt = lw.hs_qt;
-        qt.assign((size_t)(emax - emin + 1) * tsz + 64, 0.0);      // (+ one block of padding: k_vit_lane3's prefetch)
-        std::vector<char> eok((size_t)(emax - emin + 1), 1);
-        for (int e = emin; e <= emax; ++e)
-          eok[(size_t)(e - emin)] = ratio ? quantised_table_ratio(m, e, qt.data() + (size_t)(e - emin) * tsz)
-                                          : quantised_table(m, e, qt.data() + (size_t)(e - emin) * tsz);
-        for (int c = 0; c < sw.n_chunks; ++c)
-          if (he[(size_t)c] != TEHMM_SPEC_NONE && !eok[(size_t)(he[(size_t)c] - emin)]) he[(size_t)c] = TEHMM_SPEC_NONE;
-        HIPCHK(lw.qtabs.fill_async(qt.data(), qt.size(), st));
-        // a group whose speculated items share one binade is one work unit; the items of the others (interval
-        // heads, binade crossings) are pooled per binade and dealt out 64 to a wave
-        std::vector<std::vector<int>> pool((size_t)(emax - emin + 1));
-        for (int g = 0; g < lw.n_groups; ++g) {
-          int e1 = TEHMM_SPEC_NONE;
-          bool mixed = false;
-          const int nl = std::min(64, lw.n_items - g * 64);
-          for (int ln = 0; ln < nl; ++ln) {
-            const size_t item = (size_t)g * 64 + ln;
-            const int e = he[(size_t)(sw.h_first[lw.h_iv[item]] + lw.h_t0[item] / CS)];
-            if (e == TEHMM_SPEC_NONE) continue;
-            if (e1 == TEHMM_SPEC_NONE) e1 = e;
-            else if (e != e1) mixed = true;
-          }
-          if (e1 == TEHMM_SPEC_NONE) continue;
-          if (!mixed) { wk_g.push_back(g); wk_e.push_back(e1); continue; }
-          for (int ln = 0; ln < nl; ++ln) {
-            const size_t item = (size_t)g * 64 + ln;
-            const int e = he[(size_t)(sw.h_first[lw.h_iv[item]] + lw.h_t0[item] / CS)];
-            if (e != TEHMM_SPEC_NONE) pool[(size_t)(e - emin)].push_back((int)item);
-          }
-        }
-        std::vector<int> &wki = lw.hs_wki;
-        wki.clear();
-        for (int e = emin; e <= emax; ++e) {
-          const std::vector<int> &pl = pool[(size_t)(e - emin)];
-          for (size_t i0 = 0; i0 < pl.size(); i0 += 64) {
-            const int slot = (int)(wki.size() / 64);
-            for (size_t i = 0; i < 64; ++i) wki.push_back(i0 + i < pl.size() ? pl[i0 + i] : -1);
-            wk_g.push_back(-(1 + slot));
-            wk_e.push_back(e);
-          }
-        }
-        if (!wki.empty()) HIPCHK(lw.wk_items.fill_async(wki.data(), wki.size(), st));
-      }
-      {
-        // waves of one binade next to each other: they share one quantised table in the scalar cache
-        std::vector<int> ord(wk_g.size());
-        std::iota(ord.begin(), ord.end(), 0);
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return wk_e[(size_t)x] < wk_e[(size_t)y]; });
-        std::vector<int> g2(ord.size()), e2(ord.size());
-        for (size_t i = 0; i < ord.size(); ++i) { g2[i] = wk_g[(size_t)ord[i]]; e2[i] = wk_e[(size_t)ord[i]]; }
-        wk_g.swap(g2);
-        wk_e.swap(e2);
-      }
-      const int n_work = (int)wk_g.size();
-      if (n_work > 0) {
-        HIPCHK(lw.wk_g.fill_async(wk_g.data(), wk_g.size(), st));
-        HIPCHK(lw.wk_e.fill_async(wk_e.data(), wk_e.size(), st));
-      }
-      HIPCHK(hipMemcpyAsync(sw.e.p, he.data(), he.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(sw.gain.p, cgain.data(), cgain.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(sw.ok.p, 0, he.size() * sizeof(int), st));
-      HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
-      HIPCHK(hipMemsetAsync(lw.vbad.p, 0, (size_t)std::max(1, lw.n_groups) * 64 * sizeof(int), st));
-      HIPCHK(hipMemsetAsync(lw.vntie.p, 0, (size_t)std::max(1, lw.n_groups) * 64 * sizeof(int), st));
-      rc = vit_lane_upload_args(b, vc, st);
-      if (rc) return rc;
-      if (split_post) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
-#define CALL(NT_) launch_vit_lane<NT_>(b, m, iv, vc, true, ratio, WuV, n_work, (const double *)lw.qtabs.p, emin, (const int *)nullptr, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    }
-    if (vlane && dev_place) {
-      int n_work_max = 0;
-      rc = launch_vit_place(b, m, iv, CS, ratio, st, &n_work_max);
-      if (rc) return rc;
-      if (split_post) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
-#define CALL(NT_) launch_vit_lane<NT_>(b, m, iv, vc, true, ratio, WuV, n_work_max, (const double *)m->qall[ratio ? 1 : 0].p, TEHMM_SPEC_MIN_E, (const int *)&lw.place.p->n_work, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    }
-    if (vlane) {
-#define CALL(NT_) launch_vit_stitch<NT_>(b, m, iv, vc, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->ev[eV + 3], st);
-      if (defer_post) {
-        (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
-        rc = enqueue_posterior(split_post ? 2 : 0);
-        if (rc) return rc;
-      }
-#define CALL(NT_) launch_vit_fix<NT_>(b, m, iv, em, vc, true, ratio, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    } else if (vspec) {
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<int> &he = lw.hs_e;
-      if (glane) {
-        std::vector<double> &cgain = lw.hs_cgain;
-        chunk_gains(cgain);
-        spec_assign_binades(b, cgain, he);
-        HIPCHK(hipMemcpyAsync(sw.gain.p, cgain.data(), cgain.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      } else {
-        spec_assign_binades(b, gain, he);
-      }
-      HIPCHK(hipMemcpyAsync(sw.e.p, he.data(), he.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(sw.ok.p, 0, he.size() * sizeof(int), st));
-      HIPCHK(hipMemsetAsync(sw.stats.p, 0, 2 * sizeof(int), st));
-#define CALL(NT_) launch_vit_spec<NT_>(b, m, iv, emg, vc, true, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-      (void)hipEventRecord(b->ev[eV + 3], st);
-      if (defer_post) {
-        (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
-        rc = enqueue_posterior();
-        if (rc) return rc;
-      }
-#define CALL(NT_) launch_vit_fix<NT_>(b, m, iv, em, vc, false, false, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    } else if (coop) {
-#define CALL(NT_) launch_vit_coop<NT_>(b, m, iv, em, ratio, st)
-      TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
-    } else {
-      rc = viterbi_wide_cp(b, m, iv, em, ratio, st, b->ev[eV + 3], &wide_vit);
-      if (rc) return rc;
-      if (!wide_vit) {
-        if (SPL == 1) launch_viterbi<1>(b, m, iv, em, ratio, st);
-        else launch_viterbi<2>(b, m, iv, em, ratio, st);
-      }
-      if (wide_defer) {
-        // the posterior passes go behind the quantised Viterbi pass, next to the exact chain (few CUs, latency-bound)
-        if (wide_vit) (void)hipStreamWaitEvent(b->sP, b->ev[eV + 3], 0);
-        rc = enqueue_posterior();
-        if (rc) return rc;
-      }
-    }
-    (void)hipEventRecord(b->ev[eV + 1], st);
-    allow_lds(k_tb_compose<uint8_t>, 4 * TEHMM_TB_STAGE);
-    allow_lds(k_tb_fill<uint8_t>, 4 * TEHMM_TB_STAGE);
-    if (b->n_chunks > 0)
-      hipLaunchKernelGGL(k_tb_compose<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv, b->d_chunk_iv.p,
-                         b->d_chunk0.p, b->n_chunks, m->N, m->NP, b->TBW, b->tb.p, b->G.p);
-    {
-      // long intervals: two-level scan (tiles of 64 chunk maps composed in parallel)
-      int64_t maxc = 0;
-      for (int i = 0; i < b->n; ++i) maxc = std::max<int64_t>(maxc, b->h_chunk0[(size_t)i + 1] - b->h_chunk0[(size_t)i]);
-      const int maxt = (int)((maxc + 63) / 64);
-      if (maxt > 8 && maxt <= 65535) {          // (grid.y limit: longer intervals keep the one-level scan)
-        const size_t ntile = (size_t)b->n_chunks / 64 + (size_t)b->n + 2;
-        HIPCHK(b->Gg.ensure(ntile * m->NP));
-        HIPCHK(b->tstate.ensure(ntile));
-        hipLaunchKernelGGL(k_tb_group<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->G.p,
-                           b->Gg.p);
-        hipLaunchKernelGGL(k_tb_scan_top<uint8_t>, dim3(b->n), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP, (const uint8_t *)b->Gg.p,
-                           (const int *)b->last_state.p, b->tstate.p, b->paths.p);
-        hipLaunchKernelGGL(k_tb_scan_tiles<uint8_t>, dim3(b->n, maxt), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
-                           (const uint8_t *)b->G.p, (const uint8_t *)b->tstate.p, b->bstate.p);
-      } else {
-        hipLaunchKernelGGL(k_tb_scan<uint8_t>, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, b->d_chunk0.p, m->NP,
-                           b->G.p, b->last_state.p, b->bstate.p, b->paths.p);
-      }
-    }
-    if (b->n_chunks > 0)
-      hipLaunchKernelGGL(k_tb_fill<uint8_t>, dim3((b->n_chunks + 3) / 4), dim3(256), 4 * tb_stage_bytes(b->TBW), st, iv,
-                         b->n_chunks, b->d_chunk_iv.p, b->d_chunk0.p, b->TBW, b->tb.p, b->bstate.p,
-                         b->paths.p);
-    (void)hipEventRecord(b->ev[eV + 2], st);
-    if (vlane || glane) {
-      b->tnames.push_back("emission_rows");
-      b->tpairs.push_back({eV, eV + 4});
-      b->tnames.push_back("viterbi_speculate");
-      b->tpairs.push_back({eV + 4, eV + 3});
-      b->tnames.push_back("viterbi");
-      b->tpairs.push_back({eV + 3, eV + 1});
-    } else if (vspec) {
-      b->tnames.push_back("viterbi_speculate");
-      b->tpairs.push_back({eV, eV + 3});
-      b->tnames.push_back("viterbi");
-      b->tpairs.push_back({eV + 3, eV + 1});
-    } else {
-      b->tnames.push_back("viterbi");
-      b->tpairs.push_back({eV, eV + 1});
-    }
-    b->tnames.push_back("traceback");
-    b->tpairs.push_back({eV + 1, eV + 2});
-  }
-  rc = finish_wide_posterior();
+  rc = eval_emis_p0(c);
   if (rc) return rc;
-  if (postr) {
-    if (flane && fused_fb) {
-      b->tnames.push_back("forward_pass");               // lane pass + links + exact forward chain
-      b->tpairs.push_back({10, eP + 3});
-      b->tnames.push_back("backward_posterior_pass");    // lane pass incl. the posterior rows + links
-      b->tpairs.push_back({split_post ? 11 : eP + 3, eP + 1});
-    } else if (flane) {
-      if (!vlane && !glane) {
-        b->tnames.push_back("emission_rows");
-        b->tpairs.push_back({eP, eP + 4});
-      }
-      b->tnames.push_back("forward_backward_speculate");
-      b->tpairs.push_back({10, eP + 3});
-      b->tnames.push_back("forward_backward");
-      b->tpairs.push_back({eP + 3, eP + 1});
-    } else if (fspec) {
-      b->tnames.push_back("forward_backward_speculate");
-      b->tpairs.push_back({eP, eP + 3});
-      b->tnames.push_back("forward_backward");
-      b->tpairs.push_back({eP + 3, eP + 1});
-    } else {
-      b->tnames.push_back(coop ? "forward_backward" : "forward");
-      b->tpairs.push_back({eP, eP + 1});
-    }
-    b->tnames.push_back(flane && fused_fb ? "backward_chain" : (coop ? "posterior_combine" : "backward_posterior"));
-    b->tpairs.push_back({eP + 1, eP + 2});
+  if (p.postr && p.defer_post) eval_emission(c);      // the emission rows do not wait (17 ms next to P0)
+  if (p.split_post) {
+    rc = eval_posterior(c, 1);
+    if (rc) return rc;
+  } else if (p.postr && p.defer_post && p.flane && p.fused_fb) {
+    // neither do the index records of the fused passes: they only read the observations
+    FusedOrder fo_unused;
+    nt_dispatch(m->NP, [&](auto nt) { rc = fused_prepare<nt>(b, m, c.iv, c.WuF, b->sP, fo_unused); });
+    if (rc) return rc;
   }
+  if (p.postr && !p.defer_post) {
+    eval_emission(c);
+    if (!p.wide_defer) {
+      rc = eval_posterior(c, 0);
+      if (rc) return rc;
+    }
+  }
+  if (p.vit) {
+    rc = eval_viterbi(c);
+    if (rc) return rc;
+  }
+  rc = eval_finish_wide(c);
+  if (rc) return rc;
+  eval_timings(p, b);
   HIPCHK(hipGetLastError());
-  if (flags & TEHMM_EVAL_VITERBI) HIPCHK(hipStreamSynchronize(b->sV));
-  if (flags & TEHMM_EVAL_POSTERIOR) HIPCHK(hipStreamSynchronize(b->sP));
+  if (p.vit) HIPCHK(hipStreamSynchronize(b->sV));
+  if (p.postr) HIPCHK(hipStreamSynchronize(b->sP));
   for (auto &pr : b->tpairs) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, b->ev[pr.first], b->ev[pr.second]);
     b->tms.push_back((double)ms);
   }
-  if (flane && std::getenv("TEHMM_SPEC_DEBUG")) {
-    const size_t nc = (size_t)sw.n_chunks;
-    std::vector<int> re(nc), rb(nc), lf(nc), lb(nc), of(nc), ob(nc);
-    HIPCHK(hipMemcpy(re.data(), lw.runend_f.p, nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rb.data(), lw.runstart_b.p, nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lf.data(), lw.link_f.p, nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lb.data(), lw.link_b.p, nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(of.data(), lw.ok_f.p, nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ob.data(), lw.ok_b.p, nc * 4, hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < nc && c < 48; ++c)
-      std::fprintf(stderr, "[fb runs] c %zu ok_f %d link_f %d runend_f %d | ok_b %d link_b %d runstart_b %d\n", c, of[c],
-                   lf[c], re[c], ob[c], lb[c], rb[c]);
-  }
-  if (fspec) {
-    int st[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(st, b->sw.stats.p + 2, sizeof(st), hipMemcpyDeviceToHost));
-    b->tnames.push_back("count:forward_exact_blocks");
-    b->tms.push_back((double)st[0]);
-    b->tnames.push_back("count:forward_chunk_jumps");
-    b->tms.push_back((double)st[1]);
-    b->tnames.push_back("count:backward_exact_blocks");
-    b->tms.push_back((double)st[2]);
-    b->tnames.push_back("count:backward_chunk_jumps");
-    b->tms.push_back((double)st[3]);
-  }
-  if (wide_cp) {
-    b->tnames.push_back("count:wide_chunk_parallel_warmup");
-    b->tms.push_back((double)b->ww.wu_ok);
-  }
-  if (wide_vit) {
-    int st2[2] = {0, 0};
-    HIPCHK(hipMemcpy(st2, b->sw.stats.p, sizeof(st2), hipMemcpyDeviceToHost));
-    b->tnames.push_back("count:viterbi_exact_blocks");
-    b->tms.push_back((double)st2[0]);
-    b->tnames.push_back("count:viterbi_chunk_jumps");
-    b->tms.push_back((double)st2[1]);
-  }
-  if (vspec) {
-    // counters (not times): 64-position blocks the exact chain ran / chunks it could jump over
-    int st[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(st, b->sw.stats.p, sizeof(st), hipMemcpyDeviceToHost));
-#ifdef TEHMM_CHAIN_PROF
-    {
-      int pr[4];
-      HIPCHK(hipMemcpy(pr, b->sw.stats.p + 8, sizeof(pr), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemset(b->sw.stats.p + 8, 0, sizeof(pr)));
-      std::fprintf(stderr, "[chain prof] summed over intervals, ms: prologue %.2f steps %.2f barrier %.2f\n", pr[0] * 1e-4,
-                   pr[1] * 1e-4, pr[2] * 1e-4);
-    }
-#endif
-    if (std::getenv("TEHMM_SPEC_DEBUG")) {
-      std::vector<int> he((size_t)b->sw.n_chunks), hok((size_t)b->sw.n_chunks);
-      HIPCHK(hipMemcpy(he.data(), b->sw.e.p, he.size() * sizeof(int), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hok.data(), b->sw.ok.p, hok.size() * sizeof(int), hipMemcpyDeviceToHost));
-      int na = 0, nok = 0;
-      for (size_t i = 0; i < he.size(); ++i) {
-        na += he[i] != TEHMM_SPEC_NONE;
-        nok += he[i] != TEHMM_SPEC_NONE && hok[i];
-      }
-      std::fprintf(stderr, "[tehmm spec] chunks %d, speculated %d, usable %d, jumped %d, exact blocks %d\n",
-                   b->sw.n_chunks, na, nok, st[1], st[0]);
-      if (vlane) {
-        // what ends the verified runs: ties inside chunks, chunks that do not link to their predecessor
-        std::vector<int> hnt(he.size()), hcl(he.size());
-        HIPCHK(hipMemcpy(hnt.data(), b->sw.ntie.p, hnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hcl.data(), b->sw.clink.p, hcl.size() * sizeof(int), hipMemcpyDeviceToHost));
-        long ties = 0, tchunks = 0, unlinked = 0, unl_samee = 0;
-        for (size_t i = 0; i < he.size(); ++i) {
-          if (he[i] == TEHMM_SPEC_NONE || !hok[i]) continue;
-          ties += hnt[i];
-          tchunks += hnt[i] > 0;
-          if (!hcl[i]) {
-            ++unlinked;
-            if (i > 0 && he[i - 1] == he[i] && hok[i - 1]) ++unl_samee;
-          }
-        }
-        std::fprintf(stderr, "[tehmm spec] ties %ld in %ld chunks, unlinked chunks %ld (%ld next to a usable chunk of the same binade)\n",
-                     ties, tchunks, unlinked, unl_samee);
-      }
-    }
-    b->tnames.push_back("count:viterbi_exact_blocks");
-    b->tms.push_back((double)st[0]);
-    b->tnames.push_back("count:viterbi_chunk_jumps");
-    b->tms.push_back((double)st[1]);
-  }
-  if ((flags & TEHMM_EVAL_VITERBI) && viterbi_logprob)
+  rc = eval_counters(c);
+  if (rc) return rc;
+  if (p.vit && viterbi_logprob)
     HIPCHK(hipMemcpy(viterbi_logprob, b->vit_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
-  if (flags & TEHMM_EVAL_POSTERIOR) {
+  if (p.postr) {
     b->h_fwd_lp.resize((size_t)b->n);
     HIPCHK(hipMemcpy(b->h_fwd_lp.data(), b->fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
     if (forward_logprob) std::memcpy(forward_logprob, b->h_fwd_lp.data(), (size_t)b->n * sizeof(double));
@@ -4028,9 +3996,10 @@ static int launch_estep_reduce(tehmm_batch *b, const tehmm_model *m, const Inter
 // returns TEHMM_OK and *done = true when the fused path ran; *done = false: the caller falls back
 static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, double *lp_out, int *dead_out, bool *done) {
   *done = false;
-  const int CS = spec_chunk_size();
+  const EvalKnobs kn = read_eval_knobs();
+  const int CS = kn.spec_chunk;
   if (!estep_fused_wanted(m, b, false, CS)) return TEHMM_OK;
-  const int LS = lane_sub_size(CS, b->total);
+  const int LS = lane_sub_size(CS, b->total, kn.lane_sub);
   if (LS <= 0) return TEHMM_OK;
   LaneWork &lw = b->lw;
   EstepWork &w = b->ew;
@@ -4068,7 +4037,7 @@ static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, do
   fill_tabs(m, b, iv, em, false);
   SpecWork &sw = b->sw;
   int WuF = 64;
-  rc = fb_warmup(b, m, LS, iv, without_lds_tables(em), &WuF);
+  rc = fb_warmup(b, m, LS, iv, without_lds_tables(em), kn, &WuF);
   if (rc) return rc;
   FbChunks fc{};
   fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = CS;
@@ -4083,15 +4052,11 @@ static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, do
   (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
   (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
   int rcf = TEHMM_OK;
-#define CALL(NT_) rcf = launch_fused_fb<NT_>(b, m, iv, em, fc, WuF, st, b->ev[8], b->ev[6], true)
-  TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
+  nt_dispatch(m->NP, [&](auto nt) { rcf = launch_fused_fb<nt>(b, m, iv, em, fc, WuF, st, b->ev[8], b->ev[6], true); });
   if (rcf) return rcf;
   (void)hipEventRecord(b->ev[7], st);
   int rcr = TEHMM_OK;
-#define CALL(NT_) rcr = launch_estep_reduce<NT_>(b, m, iv, dev_stats, st)
-  TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
+  nt_dispatch(m->NP, [&](auto nt) { rcr = launch_estep_reduce<nt>(b, m, iv, dev_stats, st); });
   if (rcr) return rcr;
   (void)hipEventRecord(b->ev[9], st);
   HIPCHK(hipGetLastError());
@@ -4355,9 +4320,6 @@ static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *de
     w.pp_active = false;
     ++attempts;
     HIPCHK(hipStreamSynchronize(st));
-    if (std::getenv("TEHMM_SPEC_DEBUG"))
-      std::fprintf(stderr, "[tehmm wide estep] NPW %d L %d Wu %d: impossible rows in %d items, failed links %d of %d items\n", NPW,
-                   L, Wu, w.h_flags[0], w.h_flags[1], w.n_items);
     if (w.h_flags[0] > 0) return TEHMM_OK;             // impossible rows: the sequential kernels own their semantics
     if (w.h_flags[1] == 0) break;
     if (Wu >= kWuMax) return TEHMM_OK;                 // does not forget: the caller falls back
@@ -4511,9 +4473,7 @@ static int estep_accumulate(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, 
     giv.order = w.order.p;
     giv.out0 = w.grow0.p;
     const int n_iv = (int)g_order.size(), n_chunks = (int)chunk_iv.size();
-#define CALL(NT_) launch_estep<NT_>(m, giv, em, ratio, n_iv, n_chunks, w, b->ratios.p, b->sP)
-    TEHMM_NT_DISPATCH(m->NP, CALL)
-#undef CALL
+    nt_dispatch(m->NP, [&](auto nt) { launch_estep<nt>(m, giv, em, ratio, n_iv, n_chunks, w, b->ratios.p, b->sP); });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->sP));
     std::vector<double> lp((size_t)b->n);

@@ -285,9 +285,9 @@ CHUNK_CONFIGS = [
     {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "128", "TEHMM_LANE_WARMUP": "24",
      "TEHMM_LANE_VIT": "0", "TEHMM_LANE_P0": "0"},                              # short warm-up: links fail
     {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64"},                        # + lane = item exact Viterbi
-    {"TEHMM_SPEC_CHUNK": "512", "TEHMM_LANE_SUB": "256", "TEHMM_LANE_MFMA": "1"},
-    {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "128", "TEHMM_LANE_WARMUP": "24", "TEHMM_FB_RUNS": "0"},
-    {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64", "TEHMM_VIT_RUNS": "0"},   # one verification per chunk
+    {"TEHMM_SPEC_CHUNK": "512", "TEHMM_LANE_SUB": "256"},
+    {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "128", "TEHMM_LANE_WARMUP": "24"},
+    {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64"},
     {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64", "TEHMM_FUSED": "0"},      # round-1 posterior pipeline (K > 78)
 ]
 
@@ -300,8 +300,7 @@ def test_chunk_parallel_sparse_model(hip, monkeypatch, cfg):
     from tehmm_amd import synth
     from tehmm_amd.engine import HipBatch, HipModel
     from oracle import oracle
-    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-              "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED"):
+    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED"):
         monkeypatch.delenv(k, raising=False)
     for k, v in CHUNK_CONFIGS[cfg].items():
         monkeypatch.setenv(k, v)
@@ -330,8 +329,7 @@ def test_chunk_parallel_deep_emission_drops(hip, monkeypatch, cfg):
     from tehmm_amd import synth
     from tehmm_amd.engine import HipBatch, HipModel
     from oracle import oracle
-    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-              "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED"):
+    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED"):
         monkeypatch.delenv(k, raising=False)
     for k, v in CHUNK_CONFIGS[cfg].items():
         monkeypatch.setenv(k, v)
@@ -362,8 +360,7 @@ def test_chunk_parallel_paths(hip, monkeypatch, cfg, N):
     from tehmm_amd import synth
     from tehmm_amd.engine import HipBatch, HipModel
     from oracle import oracle
-    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-              "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED"):
+    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED"):
         monkeypatch.delenv(k, raising=False)
     for k, v in CHUNK_CONFIGS[cfg].items():
         monkeypatch.setenv(k, v)
@@ -402,8 +399,7 @@ def test_config_sizes_chunk_parallel_vs_sequential(hip, monkeypatch):
     starts and ends, chunk and item boundaries, interior) to 1e-6, every row sums to 1."""
     from tehmm_amd import synth
     from tehmm_amd.engine import HipBatch, HipModel
-    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-              "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED"):
+    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED"):
         monkeypatch.delenv(k, raising=False)
     model = synth.make_model(35, synth.CONFIG2_SYMBOLS, synth.CONFIG2_GAUSSIAN, seed=0)
     rs = np.random.RandomState(123)
@@ -449,8 +445,7 @@ def test_chunk_parallel_call_sequences(hip, monkeypatch):
     from tehmm_amd import synth
     from tehmm_amd.engine import HipBatch, HipModel
     from oracle import oracle
-    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-              "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED"):
+    for k in ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED"):
         monkeypatch.delenv(k, raising=False)
     model = synth.make_model(35, seed=9)
     lens = [3000, 26000, 50000]

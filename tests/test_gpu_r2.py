@@ -347,8 +347,7 @@ def test_long_interval_model_variants_vs_oracle(variant):
     assert res["viterbi_logprob"][0] == lp_o
 
 
-SPEC_ENV = ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0",
-            "TEHMM_LANE_MFMA", "TEHMM_FB_RUNS", "TEHMM_VIT_RUNS", "TEHMM_FUSED")
+SPEC_ENV = ("TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_LANE_WARMUP", "TEHMM_LANE_VIT", "TEHMM_LANE_P0", "TEHMM_FUSED")
 
 
 def _mixed_ratios(T, seed, big=False):
@@ -366,7 +365,7 @@ def _mixed_ratios(T, seed, big=False):
 
 @pytest.mark.parametrize("N,env,big", [
     (35, {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64"}, False),
-    (35, {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64", "TEHMM_VIT_RUNS": "0"}, True),
+    (35, {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64"}, True),
     (35, {"TEHMM_SPEC_CHUNK": "1024"}, True),
     (20, {"TEHMM_SPEC_CHUNK": "512", "TEHMM_LANE_SUB": "128"}, False),
     (7, {"TEHMM_SPEC_CHUNK": "256", "TEHMM_LANE_SUB": "64"}, True),

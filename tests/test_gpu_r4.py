@@ -1,6 +1,6 @@
 """Round-4 GPU tests (through the C ABI): the three-wave quantised Viterbi pass and emission + P0 kernels against the
-oracle and against the one-wave kernels (even and uneven splits of the output groups, segment ratios), binade placement
-on the device against the host placement, bit-reproducible E-step statistics, the count-static fused passes on ragged
+oracle and against the one-wave emission + P0 kernel (even and uneven splits of the output groups, segment ratios),
+binade placement on the device against the host placement, bit-reproducible E-step statistics, the count-static fused passes on ragged
 intervals."""
 import numpy as np
 import pytest
@@ -17,7 +17,7 @@ def hip():
         pytest.fail("no GPU visible: the HIP path has no CPU fallback")
 
 
-KNOBS = ("TEHMM_P2_SPLIT", "TEHMM_EMIS_SPLIT", "TEHMM_DEVICE_PLACE", "TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_DEFER",
+KNOBS = ("TEHMM_EMIS_SPLIT", "TEHMM_DEVICE_PLACE", "TEHMM_SPEC_CHUNK", "TEHMM_LANE_SUB", "TEHMM_DEFER",
          "TEHMM_LANE_VIT", "TEHMM_ESTEP_FUSED", "TEHMM_SOFT_TIES")
 
 
@@ -50,7 +50,7 @@ def _eval(model, obs, offs, ratios=None, **kw):
 @pytest.mark.parametrize("N,ratio", [(9, False), (13, False), (35, False), (35, True), (38, False), (50, True), (60, False)])
 def test_three_wave_passes_bit_exact(monkeypatch, N, ratio):
     """k_vit_lane3 (quantised pass split over three waves) and k_emis_gain_lane3 against the oracle, bit for bit, and
-    against the one-wave kernels: same paths, same scores, the same number of exact blocks left to the chain."""
+    with the one-wave emission + P0 kernel: same paths, same scores, the same number of exact blocks left to the chain."""
     from oracle import oracle
     from tehmm_amd import synth
     for k in KNOBS:
@@ -64,9 +64,8 @@ def test_three_wave_passes_bit_exact(monkeypatch, N, ratio):
         rs = np.random.RandomState(N)
         ratios = np.minimum(1 + rs.geometric(1 / 20.0, size=int(offs[-1])), 100) / 20.0
     got = {}
-    monkeypatch.setenv("TEHMM_SOFT_TIES", "0")             # (the one-wave kernel ends a piece at every rounding tie)
-    for tag, p2, em in (("split", "1", "1"), ("one", "0", "0")):
-        monkeypatch.setenv("TEHMM_P2_SPLIT", p2)
+    monkeypatch.setenv("TEHMM_SOFT_TIES", "0")             # (every rounding tie ends a piece)
+    for tag, em in (("split", "1"), ("one", "0")):
         monkeypatch.setenv("TEHMM_EMIS_SPLIT", em)
         got[tag] = _eval(model, obs, offs, ratios, viterbi=True, posterior=False)
     for i in range(len(lens)):
