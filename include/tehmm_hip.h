@@ -33,7 +33,7 @@ extern "C" {
 #define TEHMM_ERR_UNSUPPORTED (-3) /* shape outside what the kernels support (see tehmm_max_states) */
 
 /* ---- library / device ---------------------------------------------------------------------- */
-int tehmm_abi_version(void);                 /* bumps when a signature changes or is added (4) */
+int tehmm_abi_version(void);                 /* 4; later additions (the map-decode calls) are detected by symbol */
 const char *tehmm_last_error(void);          /* thread-local message of the last failing call */
 int tehmm_device_count(int *count);          /* hipGetDeviceCount */
 int tehmm_set_device(int device);            /* hipSetDevice; one process per GPU calls this once */
@@ -176,6 +176,22 @@ int tehmm_batch_device_ptrs(tehmm_batch_t *batch, void **paths_i64, void **poste
  * Q15, is the caller's: tehmm_amd/output.py.) */
 int tehmm_batch_posterior_masksum(tehmm_batch_t *batch, const double *mask, int64_t row0, int64_t row1,
                                   double *out);
+/* BaseHMM._decode_map (basehmm.py:332-359) over every interval, from the posteriors of the last
+ * TEHMM_EVAL_POSTERIOR evaluation of this batch.  map_logprob [n_intervals] host (may be NULL) = the
+ * reference's "logprob" (sum of the row maxima, quirk Q13).  mask [N] host or NULL; with a mask the
+ * masked sums of the same rows are kept as well.  TEHMM_ERR_ARG when the batch holds no posterior result.
+ * The state of a row is np.argmax of its posteriors: the lowest index among equal maxima, the first NaN of a
+ * row that holds one.  The path has its own buffer (tehmm_batch_get_paths keeps the Viterbi path of a
+ * VITERBI|POSTERIOR evaluation); the interval sums are taken in one fixed order, so two calls agree bit for
+ * bit; the masked sums equal tehmm_batch_posterior_masksum's bit for bit.  The next tehmm_eval_batch drops
+ * the result: the two getters then return TEHMM_ERR_ARG until tehmm_batch_map_decode has run again.
+ * tehmm_batch_last_timing gains the entries "map_decode" and "map_logprob_sum". */
+int tehmm_batch_map_decode(tehmm_batch_t *batch, const double *mask, double *map_logprob);
+int tehmm_batch_get_map_paths(tehmm_batch_t *batch, int64_t row0, int64_t row1, int64_t *paths);
+int tehmm_batch_get_map_masksum(tehmm_batch_t *batch, int64_t row0, int64_t row1, double *out);
+/* array level, host buffers: states[t] = argmax_j post[t][j] (np.argmax rule), rowmax[t] (may be NULL);
+ * any N from 1 to 1024 */
+int tehmm_posterior_argmax(int64_t T, int N, const double *post, int64_t *states, double *rowmax);
 /* BED coordinates of every row of a table (:243-266): segOffsets [n_rows] (NULL: unsegmented),
  * maskOffsets [n_mask] = TrackTable.getMaskRunningOffsets() (NULL: no mask); starts / ends [n_rows]. */
 int tehmm_bed_coords(int64_t n_rows, int64_t table_start, int64_t table_end, const int64_t *segOffsets,

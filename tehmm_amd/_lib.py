@@ -54,6 +54,10 @@ SIGNATURES = {
     "tehmm_mask_table_u8": (c_int, [c_i64, c_int, u8p, c_int, u8p, u8p, i32p, u8p, i32p, i64p]),
     "tehmm_batch_get_interval_logprobs": (c_int, [vp, f64p]),
     "tehmm_batch_posterior_masksum": (c_int, [vp, f64p, c_i64, c_i64, f64p]),
+    "tehmm_batch_map_decode": (c_int, [vp, f64p, f64p]),
+    "tehmm_batch_get_map_paths": (c_int, [vp, c_i64, c_i64, i64p]),
+    "tehmm_batch_get_map_masksum": (c_int, [vp, c_i64, c_i64, f64p]),
+    "tehmm_posterior_argmax": (c_int, [c_i64, c_int, f64p, i64p, f64p]),
     "tehmm_bed_coords": (c_int, [c_i64, c_i64, c_i64, i64p, i32p, c_i64, i64p, i64p]),
     "tehmm_write_bed": (c_int, [ctypes.c_char_p, c_int, ctypes.c_char_p, c_i64, i64p, i64p, i64p, c_int,
                                 ctypes.POINTER(ctypes.c_char_p), f64p]),

@@ -12,6 +12,7 @@
 #include "tehmm_wide_estep.hip.h"
 #include "tehmm_wide.hip.h"
 #include "tehmm_large.hip.h"
+#include "tehmm_map.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -446,6 +447,11 @@ struct tehmm_batch {
   DBuf<int> last_state;
   DBuf<double> vit_lp, fwd_lp;
   DBuf<int64_t> first_good;
+  // maximum-posterior decoding of the last posterior evaluation (tehmm_batch_map_decode): its own buffers, so that one
+  // VITERBI|POSTERIOR evaluation yields both decodings; map_valid falls with every later evaluation
+  DBuf<int64_t> map_paths;
+  DBuf<double> map_max, map_msum, map_lp, map_mask;
+  bool map_valid = false, map_has_mask = false;
   hipStream_t sV = nullptr, sP = nullptr, sB = nullptr;
   void *stage[2] = {nullptr, nullptr};     // pinned staging buffers of the D2H path (allocated on first use)
   hipEvent_t evX[2] = {nullptr, nullptr};
@@ -3312,6 +3318,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   if (m->K != b->K) return fail(TEHMM_ERR_ARG, "tehmm_eval_batch: model/batch track count differ");
   if (!(flags & (TEHMM_EVAL_VITERBI | TEHMM_EVAL_POSTERIOR)))
     return fail(TEHMM_ERR_ARG, "tehmm_eval_batch: nothing to do");
+  b->map_valid = false;
   b->tnames.clear();
   b->tpairs.clear();
   b->tms.clear();
@@ -3609,6 +3616,103 @@ int tehmm_batch_posterior_masksum(tehmm_batch_t *b, const double *mask, int64_t 
                      (const double *)(b->post.p + (size_t)row0 * b->N), (const double *)d_mask.p, d_out.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, d_out.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
+  return TEHMM_OK;
+}
+
+// ---- maximum-posterior decoding (basehmm.py:332-359; kernels in tehmm_map.hip.h) ---------------------------
+int tehmm_batch_map_decode(tehmm_batch_t *b, const double *mask, double *map_logprob) {
+  if (!b) return fail(TEHMM_ERR_ARG, "tehmm_batch_map_decode: NULL handle");
+  b->map_valid = false;
+  if (!b->post.p || b->total <= 0 || b->N <= 0)
+    return fail(TEHMM_ERR_ARG, "tehmm_batch_map_decode: no posterior result in this batch");
+  const int64_t rows = b->total;
+  hipStream_t st = b->sP;
+  if (!b->map_paths.p) {
+    HIPCHK(b->map_paths.alloc((size_t)rows + 1));
+    HIPCHK(b->map_max.alloc((size_t)rows + 1));
+    HIPCHK(b->map_lp.alloc((size_t)b->n + 1));
+  }
+  if (mask) {
+    if (!b->map_msum.p) HIPCHK(b->map_msum.alloc((size_t)rows + 1));
+    HIPCHK(b->map_mask.fill_async(mask, (size_t)b->N, st));
+  }
+  const dim3 grid(grid_for(rows * 64, 256, 256 * 32)), block(256);
+  const double *post = b->post.p;
+  (void)hipEventRecord(b->ev[13], st);
+  if (b->N > kMaxStates) {
+    if (mask)
+      hipLaunchKernelGGL(k_post_argmax_large<true>, grid, block, 0, st, rows, b->N, post, (const double *)b->map_mask.p,
+                         b->map_paths.p, b->map_max.p, b->map_msum.p);
+    else
+      hipLaunchKernelGGL(k_post_argmax_large<false>, grid, block, 0, st, rows, b->N, post, (const double *)nullptr,
+                         b->map_paths.p, b->map_max.p, (double *)nullptr);
+  } else {
+    if (mask)
+      hipLaunchKernelGGL(k_post_argmax<true>, grid, block, 0, st, rows, b->N, post, (const double *)b->map_mask.p,
+                         b->map_paths.p, b->map_max.p, b->map_msum.p);
+    else
+      hipLaunchKernelGGL(k_post_argmax<false>, grid, block, 0, st, rows, b->N, post, (const double *)nullptr,
+                         b->map_paths.p, b->map_max.p, (double *)nullptr);
+  }
+  (void)hipEventRecord(b->ev[14], st);
+  hipLaunchKernelGGL(k_interval_sum, dim3(b->n), block, 0, st, (const int64_t *)b->d_out0.p, (const double *)b->map_max.p,
+                     b->map_lp.p);
+  (void)hipEventRecord(b->ev[15], st);
+  HIPCHK(hipGetLastError());
+  if (map_logprob) HIPCHK(hipMemcpyAsync(map_logprob, b->map_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // the entries of this call replace those of an earlier map_decode and follow the evaluation's own
+  for (size_t i = b->tnames.size(); i-- > 0;)
+    if (b->tnames[i] == "map_decode" || b->tnames[i] == "map_logprob_sum") {
+      b->tnames.erase(b->tnames.begin() + (long)i);
+      if (i < b->tms.size()) b->tms.erase(b->tms.begin() + (long)i);
+    }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, b->ev[13], b->ev[14]);
+  b->tnames.push_back("map_decode");
+  b->tms.push_back((double)ms);
+  (void)hipEventElapsedTime(&ms, b->ev[14], b->ev[15]);
+  b->tnames.push_back("map_logprob_sum");
+  b->tms.push_back((double)ms);
+  b->map_valid = true;
+  b->map_has_mask = mask != nullptr;
+  return TEHMM_OK;
+}
+
+int tehmm_batch_get_map_paths(tehmm_batch_t *b, int64_t row0, int64_t row1, int64_t *paths) {
+  if (!b || !paths || row0 < 0 || row1 < row0 || row1 > b->total)
+    return fail(TEHMM_ERR_ARG, "tehmm_batch_get_map_paths: bad argument");
+  if (!b->map_valid) return fail(TEHMM_ERR_ARG, "tehmm_batch_get_map_paths: no maximum-posterior result in this batch");
+  return d2h(paths, b->map_paths.p + row0, (size_t)(row1 - row0) * sizeof(int64_t), b);
+}
+
+int tehmm_batch_get_map_masksum(tehmm_batch_t *b, int64_t row0, int64_t row1, double *out) {
+  if (!b || !out || row0 < 0 || row1 < row0 || row1 > b->total)
+    return fail(TEHMM_ERR_ARG, "tehmm_batch_get_map_masksum: bad argument");
+  if (!b->map_valid || !b->map_has_mask)
+    return fail(TEHMM_ERR_ARG, "tehmm_batch_get_map_masksum: no masked sums in this batch (tehmm_batch_map_decode with a mask)");
+  return d2h(out, b->map_msum.p + row0, (size_t)(row1 - row0) * sizeof(double), b);
+}
+
+int tehmm_posterior_argmax(int64_t T, int N, const double *post, int64_t *states, double *rowmax) {
+  if (T < 0 || N <= 0 || !post || !states) return fail(TEHMM_ERR_ARG, "tehmm_posterior_argmax: bad argument");
+  if (N > TEHMM_LARGE_MAX) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_posterior_argmax: N > 1024");
+  if (T == 0) return TEHMM_OK;
+  DBuf<double> d_post, d_max;
+  DBuf<int64_t> d_states;
+  HIPCHK(d_post.upload(post, (size_t)T * N));
+  HIPCHK(d_states.alloc((size_t)T));
+  if (rowmax) HIPCHK(d_max.alloc((size_t)T));
+  const dim3 grid(grid_for(T * 64, 256, 256 * 32)), block(256);
+  if (N > kMaxStates)
+    hipLaunchKernelGGL(k_post_argmax_large<false>, grid, block, 0, 0, T, N, (const double *)d_post.p, (const double *)nullptr,
+                       d_states.p, d_max.p, (double *)nullptr);
+  else
+    hipLaunchKernelGGL(k_post_argmax<false>, grid, block, 0, 0, T, N, (const double *)d_post.p, (const double *)nullptr,
+                       d_states.p, d_max.p, (double *)nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(states, d_states.p, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (rowmax) HIPCHK(hipMemcpy(rowmax, d_max.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
   return TEHMM_OK;
 }
 

@@ -335,6 +335,11 @@ class ShardedEvaluator(object):
             out["forward_logprob"] = gather_interval_scalars(mine, res["forward_logprob"], len(tables))
         if res.get("paths") is not None:
             out["paths"] = gather_paths(mine, res["paths"], lengths)
+        # maximum-posterior decoding (MultitrackHmm._eval_tables(..., map_decode=True)): states and the per-interval sums
+        if res.get("map_paths") is not None:
+            out["map_paths"] = gather_paths(mine, res["map_paths"], lengths)
+        if res.get("map_logprob") is not None:
+            out["map_logprob"] = gather_interval_scalars(mine, res["map_logprob"], len(tables))
         return mine, out
 
 

@@ -38,10 +38,12 @@ class HipModel(object):
 
     __del__ = close
 
-    def eval(self, batch, viterbi=True, posterior=True, use_ratios=True):
+    def eval(self, batch, viterbi=True, posterior=True, use_ratios=True, map_decode=False):
         """Run BaseHMM.decode and/or BaseHMM.score_samples over every interval of ``batch``.
         Returns per-interval log-probabilities; paths / posteriors stay on the device until
-        fetched with batch.paths() / batch.posteriors()."""
+        fetched with batch.paths() / batch.posteriors().  map_decode (implies posterior): the maximum-posterior
+        decoding of BaseHMM._decode_map as well -- "map_logprob" in the result, the states with batch.map_paths()."""
+        posterior = posterior or map_decode
         flags = (EVAL_VITERBI if viterbi else 0) | (EVAL_POSTERIOR if posterior else 0)
         if use_ratios:
             flags |= EVAL_USE_RATIOS
@@ -50,7 +52,10 @@ class HipModel(object):
         _lib.check(_lib.load().tehmm_eval_batch(self._h, batch._h, flags, ptr(vlp, f64p), ptr(flp, f64p)),
                    "tehmm_eval_batch")
         batch.N = self.N
-        return {"viterbi_logprob": vlp, "forward_logprob": flp}
+        out = {"viterbi_logprob": vlp, "forward_logprob": flp}
+        if map_decode:
+            out["map_logprob"] = batch.map_decode()
+        return out
 
     def estep_device(self, batch, use_ratios, stats):
         """E-step with the raw statistics ADDED into the device buffer `stats` (DeviceStats)."""
@@ -249,6 +254,39 @@ class HipBatch(object):
                    "tehmm_batch_posterior_masksum")
         return out
 
+    def map_decode(self, mask=None):
+        """BaseHMM._decode_map (basehmm.py:332-359) over every interval from the posteriors of the last evaluation,
+        on the device: returns map_logprob [n] (the sums of the row maxima, quirk Q13); the states stay on the
+        device for map_paths().  mask [N]: the masked sums of posterior_masksum in the same pass (map_masksum())."""
+        out = np.zeros(self.n, dtype=np.float64)
+        if self.n == 0 or self.total == 0:
+            return out
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.float64)
+            assert mask.shape[0] == self.N
+        _lib.check(_lib.load().tehmm_batch_map_decode(self._h, ptr(mask, f64p), ptr(out, f64p)),
+                   "tehmm_batch_map_decode")
+        return out
+
+    def map_paths(self, row0=0, row1=None, pinned=True):
+        """The maximum-posterior states of rows [row0, row1) (8 instead of 8 N bytes per row cross PCIe)."""
+        row1 = self.total if row1 is None else row1
+        big = pinned and (row1 - row0) >= (1 << 19)
+        out = _lib.pinned_empty(row1 - row0, np.int64) if big else np.empty(row1 - row0, dtype=np.int64)
+        if row1 > row0:
+            _lib.check(_lib.load().tehmm_batch_get_map_paths(self._h, row0, row1, ptr(out, i64p)),
+                       "tehmm_batch_get_map_paths")
+        return out
+
+    def map_masksum(self, row0=0, row1=None):
+        """The masked posterior sums map_decode(mask) computed along the way."""
+        row1 = self.total if row1 is None else row1
+        out = np.empty(row1 - row0, dtype=np.float64)
+        if row1 > row0:
+            _lib.check(_lib.load().tehmm_batch_get_map_masksum(self._h, row0, row1, ptr(out, f64p)),
+                       "tehmm_batch_get_map_masksum")
+        return out
+
     def device_ptrs(self):
         p, q = vp(), vp()
         _lib.check(_lib.load().tehmm_batch_device_ptrs(self._h, ctypes.byref(p), ctypes.byref(q)),
@@ -256,14 +294,14 @@ class HipBatch(object):
         return p.value, q.value
 
     def timing(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_double * 16)()
-        n = _lib.load().tehmm_batch_last_timing(self._h, 16, names, ms)
+        names = (ctypes.c_char_p * 32)()
+        ms = (ctypes.c_double * 32)()
+        n = _lib.load().tehmm_batch_last_timing(self._h, 32, names, ms)
         return {names[i].decode(): ms[i] for i in range(n)}
 
 
 def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=True, posterior=True,
-                mask=None, use_ratios=True):
+                mask=None, use_ratios=True, map_decode=False):
     """teHmmEval over host-resident intervals with the result transfer hidden behind the evaluation: the intervals
     are cut into groups of about `group_rows` positions, a worker thread creates and evaluates group g + 1 (H2D of the
     observations, tehmm_eval_batch) while this thread fetches group g's paths and posteriors over PCIe into pinned
@@ -273,9 +311,14 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
     their sum.  mask: fetch the masked posterior sums (teHmmEval.py:270-272) instead of the rows.
 
     Returns (paths list, posteriors-or-masked-sums list, viterbi_logprob, forward_logprob) in interval order; the
-    per-group arrays are views of pinned blocks."""
+    per-group arrays are views of pinned blocks.
+
+    map_decode (teHmmEval --maxPost; implies the posterior evaluation): the maximum-posterior states are reduced on the
+    device and fetched INSTEAD of the posterior rows (with `mask` the masked sums of the same pass as well; without
+    one the second list holds None), and two more values are returned: (..., map paths list, map_logprob)."""
     import threading
     import queue
+    posterior = posterior or map_decode
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     n = len(offsets) - 1
     groups, g0 = [], 0
@@ -293,15 +336,18 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
                 r0, r1 = int(offsets[a]), int(offsets[b])
                 hb = HipBatch(obs[r0:r1], offsets[a:b + 1] - offsets[a], None if ratios is None else ratios[r0:r1])
                 res = model.eval(hb, viterbi=viterbi, posterior=posterior, use_ratios=use_ratios and ratios is not None)
+                if map_decode:
+                    res["map_logprob"] = hb.map_decode(mask)
                 ready.put((a, b, hb, res, None))
         except BaseException as exc:        # (handed to the consumer: it re-raises)
             ready.put((None, None, None, None, exc))
 
     th = threading.Thread(target=producer, daemon=True)
     th.start()
-    paths, posts = [None] * n, [None] * n
+    paths, posts, mpaths = [None] * n, [None] * n, [None] * n
     vlp = np.zeros(n) if viterbi else None
     flp = np.zeros(n) if posterior else None
+    mlp = np.zeros(n) if map_decode else None
     for _ in groups:
         a, b, hb, res, exc = ready.get()
         if exc is not None:
@@ -313,11 +359,22 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
             vlp[a:b] = res["viterbi_logprob"]
             for i in range(a, b):
                 paths[i] = p[int(lo[i - a]):int(lo[i - a + 1])]
-        if posterior:
+        if map_decode:
+            p = hb.map_paths()
+            q = hb.map_masksum() if mask is not None else None
+            flp[a:b] = res["forward_logprob"]
+            mlp[a:b] = res["map_logprob"]
+            for i in range(a, b):
+                mpaths[i] = p[int(lo[i - a]):int(lo[i - a + 1])]
+                if q is not None:
+                    posts[i] = q[int(lo[i - a]):int(lo[i - a + 1])]
+        elif posterior:
             q = hb.posterior_masksum(mask) if mask is not None else hb.posteriors()
             flp[a:b] = res["forward_logprob"]
             for i in range(a, b):
                 posts[i] = q[int(lo[i - a]):int(lo[i - a + 1])]
         hb.close()
     th.join()
+    if map_decode:
+        return paths, posts, vlp, flp, mpaths, mlp
     return paths, posts, vlp, flp

@@ -113,7 +113,7 @@ class MultitrackHmm(BaseHMM):
         assert numThreads == 1
         tables = trackData.getTrackTableList()
         if self._algorithm == "map":
-            out = [self.decode(t) for t in tables]
+            out = self._map_decode_tables(tables)
         else:
             res = self._eval_tables(tables, viterbi=True, posterior=False)
             out = list(zip(res["viterbi_logprob"], res["paths"]))
@@ -124,8 +124,21 @@ class MultitrackHmm(BaseHMM):
         was built with algorithm="map" (quirk Q14)."""
         if self._algorithm == "map":
             return [(p, self._name_states(s))
-                    for p, s in (self.decode(t, algorithm="map") for t in trackData.getTrackTableList())]
+                    for p, s in self._map_decode_tables(trackData.getTrackTableList())]
         return self.viterbi(trackData, numThreads)
+
+    def _map_decode_tables(self, tables):
+        """decode() of a "map" model over a list of tables: (map_logprob, states) per table from ONE fused launch
+        (the posterior rows stay on the device), with the forward log-likelihoods noted table by table in table
+        order as the reference's per-table score_samples does.  A list that cannot fuse goes table by table."""
+        if len(tables) == 0:
+            return []
+        if not self._can_fuse(tables):
+            return [self.decode(t) for t in tables]
+        res = self._eval_tables(tables, viterbi=False, posterior=False, map_decode=True)
+        for lp in res["forward_logprob"]:
+            self._note_forward_logprob(lp)
+        return list(zip(res["map_logprob"], res["map_paths"]))
 
     def posteriorDistribution(self, trackData):
         """Posterior [T, N] per table (hmm.py:254-263) -- all tables in one fused launch."""
@@ -210,24 +223,32 @@ class MultitrackHmm(BaseHMM):
                 return False
         return True
 
-    def _eval_tables(self, tables, viterbi, posterior):
+    def _eval_tables(self, tables, viterbi, posterior, map_decode=False):
         """decode and/or score_samples over a list of tables.  Ratio semantics exactly as the
         reference drivers: emission never sees ratios; Viterbi transitions do (Q11); posteriors
-        never (Q12)."""
+        never (Q12).  map_decode: BaseHMM._decode_map as well ("map_paths", "map_logprob"), reduced on the device
+        from the posteriors -- which never see ratios, so tables with and without them share the launch; the
+        posterior rows come to the host only when `posterior` asks for them."""
         if len(tables) == 0:
             return {"viterbi_logprob": np.zeros(0), "paths": [], "forward_logprob": np.zeros(0),
-                    "posteriors": []}
+                    "posteriors": [], "map_paths": [], "map_logprob": np.zeros(0)}
         if not self._can_fuse(tables):
             out = {"viterbi_logprob": [], "paths": [], "forward_logprob": [], "posteriors": []}
+            if map_decode:
+                out.update({"map_paths": [], "map_logprob": []})
             for t in tables:
                 if viterbi:
                     lp, s = self._decode_viterbi(t)
                     out["viterbi_logprob"].append(lp)
                     out["paths"].append(s)
-                if posterior:
+                if posterior or map_decode:
                     lp, p = BaseHMM.score_samples(self, t)
                     out["forward_logprob"].append(lp)
-                    out["posteriors"].append(p)
+                    if posterior:
+                        out["posteriors"].append(p)
+                    if map_decode:
+                        out["map_paths"].append(np.argmax(p, axis=1))
+                        out["map_logprob"].append(np.max(p, axis=1).sum())
             return out
         from .engine import HipBatch
         arrays = [t.getNumPyArray() if isinstance(t, TrackTable) else np.ascontiguousarray(t)
@@ -242,15 +263,15 @@ class MultitrackHmm(BaseHMM):
             # would skip every ratio branch; keep exactness by evaluating such tables separately
             if any(r is None for r in ratios):
                 res_a = self._eval_tables([t for t, r in zip(tables, ratios) if r is not None],
-                                          viterbi, posterior)
+                                          viterbi, posterior, map_decode)
                 res_b = self._eval_tables([t for t, r in zip(tables, ratios) if r is None],
-                                          viterbi, posterior)
+                                          viterbi, posterior, map_decode)
                 return _merge_results(res_a, res_b, [r is not None for r in ratios])
             rcat = np.concatenate(ratios)
         obs = np.concatenate(arrays, axis=0) if len(arrays) > 1 else arrays[0]
         hm = self._device_model()
         hb = HipBatch(obs, offs, rcat)
-        res = hm.eval(hb, viterbi=viterbi, posterior=posterior, use_ratios=use_ratios)
+        res = hm.eval(hb, viterbi=viterbi, posterior=posterior, use_ratios=use_ratios, map_decode=map_decode)
         out = dict(res)
         if viterbi:
             p = hb.paths()
@@ -258,16 +279,25 @@ class MultitrackHmm(BaseHMM):
         if posterior:
             q = hb.posteriors()
             out["posteriors"] = [q[offs[i]:offs[i + 1]] for i in range(len(lens))]
+        if map_decode:
+            p = hb.map_paths()
+            out["map_paths"] = [p[offs[i]:offs[i + 1]] for i in range(len(lens))]
         hb.close()
         return out
 
     def decode(self, obs, algorithm="viterbi"):
-        """BaseHMM.decode (basehmm.py:361-396), fused on the device for the Viterbi case."""
+        """BaseHMM.decode (basehmm.py:361-396), fused on the device: the Viterbi path, or with the effective
+        algorithm "map" the maximum-posterior states (the nested score_samples of _decode_map notes the table's
+        forward log-likelihood; so does this)."""
         if self._algorithm in ("viterbi", "map"):
             algorithm = self._algorithm
         if algorithm == "viterbi" and self._can_fuse([obs]):
             res = self._eval_tables([obs], viterbi=True, posterior=False)
             return res["viterbi_logprob"][0], res["paths"][0]
+        if algorithm == "map" and self._can_fuse([obs]):
+            res = self._eval_tables([obs], viterbi=False, posterior=False, map_decode=True)
+            self._note_forward_logprob(res["forward_logprob"][0])
+            return res["map_logprob"][0], res["map_paths"][0]
         return BaseHMM.decode(self, obs, algorithm)
 
     def score_samples(self, obs):
