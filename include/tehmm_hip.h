@@ -33,7 +33,7 @@ extern "C" {
 #define TEHMM_ERR_UNSUPPORTED (-3) /* shape outside what the kernels support (see tehmm_max_states) */
 
 /* ---- library / device ---------------------------------------------------------------------- */
-int tehmm_abi_version(void);                 /* 4; later additions (the map-decode calls) are detected by symbol */
+int tehmm_abi_version(void);                 /* 4; later additions (map decode, emission distribution) are detected by symbol */
 const char *tehmm_last_error(void);          /* thread-local message of the last failing call */
 int tehmm_device_count(int *count);          /* hipGetDeviceCount */
 int tehmm_set_device(int device);            /* hipSetDevice; one process per GPU calls this once */
@@ -192,6 +192,23 @@ int tehmm_batch_get_map_masksum(tehmm_batch_t *batch, int64_t row0, int64_t row1
 /* array level, host buffers: states[t] = argmax_j post[t][j] (np.argmax rule), rowmax[t] (may be NULL);
  * any N from 1 to 1024 */
 int tehmm_posterior_argmax(int64_t T, int N, const double *post, int64_t *states, double *rowmax);
+/* MultitrackHmm.emissionDistribution + the --ed column (hmm.py:265-277, teHmmEval.py:273-275), from the packed
+ * observations of the batch and the emission rows of the model; any N from 1 to 1024, no prior tehmm_eval_batch needed,
+ * and no evaluation result of the batch (paths, posteriors, map result) is touched.
+ *   tehmm_batch_get_emissions:    frame [row1 - row0][N] host = the rows fastAllLogProbs writes, bit for bit;
+ *   tehmm_batch_emission_masksum: out [row1 - row0] host, out[r] = log(sum_j exp(frame[r][j]) * mask[j]) (mask [N] host),
+ *                                 -inf where the sum is 0: 8 instead of 8 N bytes per row cross PCIe.
+ * Rows [row0, row1) of the concatenation; the range may cross interval boundaries.  The leading-rows rule (quirk Q9: the
+ * rows before the first emittable row are all zero) is applied per INTERVAL, as the reference calls the function once
+ * per table, also when row0 lies behind an interval's leading rows.  use_ratios: multiply the rows by the batch's
+ * segRatios (emissionDistribution hands the TrackTable itself to allLogProbs, so a segmented table does get them
+ * there); TEHMM_ERR_ARG on a batch created without ratios.  Nothing is accumulated across rows: two calls agree bit for
+ * bit.  tehmm_batch_last_timing gains "emission_column" / "emission_frame" (the device passes of the last such call).
+ * (The one-row shift of the emission file, quirk Q15, is the caller's: tehmm_amd/output.py.) */
+int tehmm_batch_emission_masksum(tehmm_model_t *model, tehmm_batch_t *batch, int use_ratios, const double *mask,
+                                 int64_t row0, int64_t row1, double *out);
+int tehmm_batch_get_emissions(tehmm_model_t *model, tehmm_batch_t *batch, int use_ratios, int64_t row0, int64_t row1,
+                              double *frame);
 /* BED coordinates of every row of a table (:243-266): segOffsets [n_rows] (NULL: unsegmented),
  * maskOffsets [n_mask] = TrackTable.getMaskRunningOffsets() (NULL: no mask); starts / ends [n_rows]. */
 int tehmm_bed_coords(int64_t n_rows, int64_t table_start, int64_t table_end, const int64_t *segOffsets,

@@ -58,6 +58,8 @@ SIGNATURES = {
     "tehmm_batch_get_map_paths": (c_int, [vp, c_i64, c_i64, i64p]),
     "tehmm_batch_get_map_masksum": (c_int, [vp, c_i64, c_i64, f64p]),
     "tehmm_posterior_argmax": (c_int, [c_i64, c_int, f64p, i64p, f64p]),
+    "tehmm_batch_emission_masksum": (c_int, [vp, vp, c_int, f64p, c_i64, c_i64, f64p]),
+    "tehmm_batch_get_emissions": (c_int, [vp, vp, c_int, c_i64, c_i64, f64p]),
     "tehmm_bed_coords": (c_int, [c_i64, c_i64, c_i64, i64p, i32p, c_i64, i64p, i64p]),
     "tehmm_write_bed": (c_int, [ctypes.c_char_p, c_int, ctypes.c_char_p, c_i64, i64p, i64p, i64p, c_int,
                                 ctypes.POINTER(ctypes.c_char_p), f64p]),

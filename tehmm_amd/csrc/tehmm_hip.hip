@@ -13,6 +13,7 @@
 #include "tehmm_wide.hip.h"
 #include "tehmm_large.hip.h"
 #include "tehmm_map.hip.h"
+#include "tehmm_edist.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -452,6 +453,10 @@ struct tehmm_batch {
   DBuf<int64_t> map_paths;
   DBuf<double> map_max, map_msum, map_lp, map_mask;
   bool map_valid = false, map_has_mask = false;
+  // emission distribution (tehmm_batch_emission_masksum / tehmm_batch_get_emissions): scratch of its own, so that no
+  // evaluation result of the batch is touched
+  DBuf<unsigned long long> ed_first;
+  DBuf<double> ed_mask, ed_col;
   hipStream_t sV = nullptr, sP = nullptr, sB = nullptr;
   void *stage[2] = {nullptr, nullptr};     // pinned staging buffers of the D2H path (allocated on first use)
   hipEvent_t evX[2] = {nullptr, nullptr};
@@ -3714,6 +3719,89 @@ int tehmm_posterior_argmax(int64_t T, int N, const double *post, int64_t *states
   HIPCHK(hipMemcpy(states, d_states.p, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (rowmax) HIPCHK(hipMemcpy(rowmax, d_max.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
   return TEHMM_OK;
+}
+
+// ---- emission distribution and the --ed column (hmm.py:265-277, teHmmEval.py:273-275; kernels in tehmm_edist.hip.h) ----
+namespace {
+template <int W, int SPL>
+void launch_edist(bool col, dim3 grid, hipStream_t st, const IntervalTab &iv, const EmisTab &em, int N, int64_t row0,
+                  int64_t row1, const unsigned long long *first, const double *mask, double *out) {
+  if (col) hipLaunchKernelGGL((k_edist<W, SPL, true>), grid, dim3(256), 0, st, iv, em, N, row0, row1, first, mask, out);
+  else hipLaunchKernelGGL((k_edist<W, SPL, false>), grid, dim3(256), 0, st, iv, em, N, row0, row1, first, mask, out);
+}
+
+// mask != NULL: the column; else the frame.  dst is a host buffer.
+int emission_dist(tehmm_model *m, tehmm_batch *b, int use_ratios, const double *mask, bool col, int64_t row0, int64_t row1,
+                  double *dst, const char *who) {
+  if (!m || !b || !dst || (col && !mask)) return fail(TEHMM_ERR_ARG, std::string(who) + ": NULL argument");
+  if (m->N > TEHMM_LARGE_MAX) return fail(TEHMM_ERR_UNSUPPORTED, std::string(who) + ": N > 1024");
+  if (m->K != b->K) return fail(TEHMM_ERR_ARG, std::string(who) + ": model/batch track count differ");
+  if (row0 < 0 || row1 < row0 || row1 > b->total) return fail(TEHMM_ERR_ARG, std::string(who) + ": bad row range");
+  if (use_ratios && !b->has_ratios) return fail(TEHMM_ERR_ARG, std::string(who) + ": the batch holds no segment ratios");
+  if (row1 == row0) return TEHMM_OK;
+  const int N = m->N;
+  const int64_t rows = row1 - row0;
+  hipStream_t st = b->sB;
+  IntervalTab iv;
+  EmisTab em;
+  fill_tabs(m, b, iv, em, use_ratios != 0);
+  // Q9 is per interval: the first-row pass starts where row0's interval starts
+  const int i0 = (int)(std::upper_bound(b->h_off.begin(), b->h_off.end(), row0) - b->h_off.begin()) - 1;
+  const int64_t rowA = b->h_off[(size_t)i0];
+  HIPCHK(b->ed_first.ensure((size_t)b->n + 1));
+  HIPCHK(hipMemcpyAsync(b->ed_first.p, b->d_len.p, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  DBuf<double> d_frame;
+  double *d_out = nullptr;
+  if (col) {
+    HIPCHK(b->ed_mask.fill_async(mask, (size_t)N, st));
+    HIPCHK(b->ed_col.ensure((size_t)rows));
+    d_out = b->ed_col.p;
+  } else {
+    HIPCHK(d_frame.alloc((size_t)rows * N));
+    d_out = d_frame.p;
+  }
+  (void)hipEventRecord(b->ev[13], st);
+  hipLaunchKernelGGL(k_edist_first, dim3(grid_for(row1 - rowA, 256, 2048)), dim3(256), 0, st, iv, em, N, rowA, row1,
+                     b->ed_first.p);
+  // lanes per row: the whole wave above 32 states, else the smallest group that holds the states and the K / 4 words
+  // of a packed observation row
+  const int need = std::max(N, em.KPW);
+  const dim3 grid(grid_for(rows, 256, 4096));
+  const unsigned long long *first = b->ed_first.p;
+  const double *dmask = col ? b->ed_mask.p : nullptr;
+  if (need <= 8) launch_edist<8, 1>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  else if (need <= 16) launch_edist<16, 1>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  else if (need <= 32) launch_edist<32, 1>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  else if (N <= 64) launch_edist<64, 1>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  else if (N <= 128) launch_edist<64, 2>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  else launch_edist<64, 4>(col, grid, st, iv, em, N, row0, row1, first, dmask, d_out);
+  (void)hipEventRecord(b->ev[14], st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  const char *name = col ? "emission_column" : "emission_frame";
+  for (size_t i = b->tnames.size(); i-- > 0;)
+    if (b->tnames[i] == name) {
+      b->tnames.erase(b->tnames.begin() + (long)i);
+      if (i < b->tms.size()) b->tms.erase(b->tms.begin() + (long)i);
+    }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, b->ev[13], b->ev[14]);
+  b->tnames.push_back(name);
+  b->tms.push_back((double)ms);
+  const int rc = d2h(dst, d_out, (size_t)rows * (col ? 1 : N) * sizeof(double), b);
+  if (!col && b->sP) (void)hipStreamSynchronize(b->sP);      // (the staged copy read the frame block on that stream)
+  return rc;
+}
+}  // namespace
+
+int tehmm_batch_emission_masksum(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, const double *mask, int64_t row0,
+                                 int64_t row1, double *out) {
+  return emission_dist(m, b, use_ratios, mask, true, row0, row1, out, "tehmm_batch_emission_masksum");
+}
+
+int tehmm_batch_get_emissions(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, int64_t row0, int64_t row1,
+                              double *frame) {
+  return emission_dist(m, b, use_ratios, nullptr, false, row0, row1, frame, "tehmm_batch_get_emissions");
 }
 
 int tehmm_bed_coords(int64_t n_rows, int64_t table_start, int64_t table_end, const int64_t *segOffsets,

@@ -329,6 +329,9 @@ class ShardedEvaluator(object):
             out["posterior_masksum"] = gather_rows(mine, res["posterior_masksum"], lengths, width=0)
         if res.get("posteriors") is not None:
             out["posteriors"] = gather_rows(mine, res["posteriors"], lengths)
+        # the masked emission column of --ed (MultitrackHmm.emissionColumn, HipBatch.emission_masksum): 8 B per row as well
+        if res.get("emission_masksum") is not None:
+            out["emission_masksum"] = gather_rows(mine, res["emission_masksum"], lengths, width=0)
         if res.get("viterbi_logprob") is not None:
             out["viterbi_logprob"] = gather_interval_scalars(mine, res["viterbi_logprob"], len(tables))
         if res.get("forward_logprob") is not None:

@@ -287,6 +287,32 @@ class HipBatch(object):
                        "tehmm_batch_get_map_masksum")
         return out
 
+    def emission_masksum(self, model, mask, use_ratios=False, row0=0, row1=None):
+        """log(sum_j exp(emissions[r, j]) * mask[j]) for rows [row0, row1) -- the 4th column of teHmmEval --ed
+        (teHmmEval.py:273-275) -- from the observations this batch holds and the emission rows of `model`, reduced on
+        the device: 8 instead of 8 N bytes per row cross PCIe.  No evaluation is needed and none is disturbed.
+        use_ratios: multiply the rows by the batch's segRatios, as emissionDistribution does for a segmented table."""
+        row1 = self.total if row1 is None else row1
+        mask = np.ascontiguousarray(mask, dtype=np.float64)
+        assert mask.shape[0] == model.N
+        out = np.empty(row1 - row0, dtype=np.float64)
+        _lib.check(_lib.load().tehmm_batch_emission_masksum(model._h, self._h, 1 if use_ratios else 0, ptr(mask, f64p),
+                                                            row0, row1, ptr(out, f64p)),
+                   "tehmm_batch_emission_masksum")
+        return out
+
+    def emissions(self, model, use_ratios=False, row0=0, row1=None, pinned=True):
+        """The emission frame [row1 - row0, N] of MultitrackHmm.emissionDistribution (hmm.py:265-277): the rows
+        fastAllLogProbs writes, with its leading-rows rule (quirk Q9) applied per interval."""
+        row1 = self.total if row1 is None else row1
+        big = pinned and (row1 - row0) * model.N >= (1 << 19)
+        out = (_lib.pinned_empty((row1 - row0, model.N), np.float64) if big
+               else np.empty((row1 - row0, model.N), dtype=np.float64))
+        _lib.check(_lib.load().tehmm_batch_get_emissions(model._h, self._h, 1 if use_ratios else 0, row0, row1,
+                                                         ptr(out, f64p)),
+                   "tehmm_batch_get_emissions")
+        return out
+
     def device_ptrs(self):
         p, q = vp(), vp()
         _lib.check(_lib.load().tehmm_batch_device_ptrs(self._h, ctypes.byref(p), ctypes.byref(q)),
@@ -301,7 +327,7 @@ class HipBatch(object):
 
 
 def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=True, posterior=True,
-                mask=None, use_ratios=True, map_decode=False):
+                mask=None, use_ratios=True, map_decode=False, ed_mask=None, ed_use_ratios=False):
     """teHmmEval over host-resident intervals with the result transfer hidden behind the evaluation: the intervals
     are cut into groups of about `group_rows` positions, a worker thread creates and evaluates group g + 1 (H2D of the
     observations, tehmm_eval_batch) while this thread fetches group g's paths and posteriors over PCIe into pinned
@@ -315,7 +341,11 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
 
     map_decode (teHmmEval --maxPost; implies the posterior evaluation): the maximum-posterior states are reduced on the
     device and fetched INSTEAD of the posterior rows (with `mask` the masked sums of the same pass as well; without
-    one the second list holds None), and two more values are returned: (..., map paths list, map_logprob)."""
+    one the second list holds None), and two more values are returned: (..., map paths list, map_logprob).
+
+    ed_mask (teHmmEval --ed/--edStates): the masked emission column of every group (HipBatch.emission_masksum, with the
+    segRatios when ed_use_ratios) is fetched on this thread like the posterior sums, and one more value is returned
+    last: the list of per-interval columns."""
     import threading
     import queue
     posterior = posterior or map_decode
@@ -348,6 +378,7 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
     vlp = np.zeros(n) if viterbi else None
     flp = np.zeros(n) if posterior else None
     mlp = np.zeros(n) if map_decode else None
+    edcols = [None] * n
     for _ in groups:
         a, b, hb, res, exc = ready.get()
         if exc is not None:
@@ -373,8 +404,11 @@ def eval_stream(model, obs, offsets, ratios=None, group_rows=4_000_000, viterbi=
             flp[a:b] = res["forward_logprob"]
             for i in range(a, b):
                 posts[i] = q[int(lo[i - a]):int(lo[i - a + 1])]
+        if ed_mask is not None:
+            q = hb.emission_masksum(model, ed_mask, use_ratios=ed_use_ratios and ratios is not None)
+            for i in range(a, b):
+                edcols[i] = q[int(lo[i - a]):int(lo[i - a + 1])]
         hb.close()
     th.join()
-    if map_decode:
-        return paths, posts, vlp, flp, mpaths, mlp
-    return paths, posts, vlp, flp
+    out = (paths, posts, vlp, flp, mpaths, mlp) if map_decode else (paths, posts, vlp, flp)
+    return out + (edcols,) if ed_mask is not None else out

@@ -146,7 +146,45 @@ class MultitrackHmm(BaseHMM):
         return res["posteriors"]
 
     def emissionDistribution(self, trackData):
-        return [self._compute_log_likelihood(t) for t in trackData.getTrackTableList()]
+        """Emission frame [T, N] per table (hmm.py:265-277).  Tables that can fuse go through one batch per ratio
+        group (the TrackTable itself reaches allLogProbs here, so a segmented table does get its ratios); the
+        others keep the per-table array-level path."""
+        tables = trackData.getTrackTableList()
+        if len(tables) == 0 or not self._can_fuse(tables):
+            return [self._compute_log_likelihood(t) for t in tables]
+        return self._emission_tables(tables, None)
+
+    def emissionColumn(self, trackData, mask):
+        """log(sum_j exp(emissions[r, j]) * mask[j]) per table row: the 4th column of teHmmEval --ed
+        (teHmmEval.py:273-275) without moving the frames -- 8 bytes per row leave the device."""
+        tables = trackData.getTrackTableList()
+        mask = np.ascontiguousarray(mask, dtype=np.float64)
+        if len(tables) == 0 or not self._can_fuse(tables):
+            with np.errstate(divide="ignore"):
+                return [np.log(np.sum(np.exp(self._compute_log_likelihood(t)) * mask, axis=1)) for t in tables]
+        return self._emission_tables(tables, mask)
+
+    def _emission_tables(self, tables, mask):
+        """Frames (mask None) or masked columns of fusable tables: one batch per ratio group, as _fused_estep."""
+        from .engine import HipBatch
+        arrays = [t.getNumPyArray() if isinstance(t, TrackTable) else np.ascontiguousarray(t) for t in tables]
+        ratios = [self.emissionModel.getSegmentRatios(t) for t in tables]
+        hm = self._device_model()
+        out = [None] * len(tables)
+        for has_r in (True, False):
+            idx = [i for i, r in enumerate(ratios) if (r is not None) == has_r]
+            if not idx:
+                continue
+            lens = np.asarray([arrays[i].shape[0] for i in idx], dtype=np.int64)
+            offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            obs = np.concatenate([arrays[i] for i in idx], axis=0)
+            rcat = np.concatenate([ratios[i] for i in idx]) if has_r else None
+            hb = HipBatch(obs, offs, rcat)
+            q = hb.emissions(hm, use_ratios=has_r) if mask is None else hb.emission_masksum(hm, mask, use_ratios=has_r)
+            for n, i in enumerate(idx):
+                out[i] = q[offs[n]:offs[n + 1]]
+            hb.close()
+        return out
 
     def getTrackList(self):
         return self.trackList

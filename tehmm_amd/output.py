@@ -41,16 +41,43 @@ def _write(path, append, chrom, starts, ends, states=None, names=None, values=No
 
 
 def statesToBed(trackTable, states, bedPath=None, posteriorSums=None, posteriorsPath=None, stateNames=None,
-                append=True):
+                append=True, emissionSums=None, emissionsPath=None):
     """teHmmEval.py:238-275.  states: integer state per row; posteriorSums: the masked posterior sum per
     row (HipBatch.posterior_masksum) -- written one row late, wrapping, as the reference does (quirk Q15:
-    row i carries posteriors[i - 1])."""
+    row i carries posteriors[i - 1]).  emissionSums: the masked emission column per row
+    (HipBatch.emission_masksum, MultitrackHmm.emissionColumn) for the --ed file, with the same one-row shift
+    (row i carries emProbs[i - 1]); -inf is written as Python 2 prints that float64."""
     starts, ends = bedCoords(trackTable)
     chrom = trackTable.getChrom()
     if bedPath is not None:
         _write(bedPath, append, chrom, starts, ends, states=states, names=stateNames)
     if posteriorSums is not None and posteriorsPath is not None:
         _write(posteriorsPath, append, chrom, starts, ends, values=np.roll(np.asarray(posteriorSums), 1))
+    if emissionSums is not None and emissionsPath is not None:
+        _write(emissionsPath, append, chrom, starts, ends, values=np.roll(np.asarray(emissionSums), 1))
+
+
+def getPosteriorsMask(pdStates, model):
+    """teHmmEval.py:294-311: mask[i] == 1 iff state i is named in the comma-separated `pdStates` (--pdStates and
+    --edStates); the states of a model without a state-name map are named "0", "1", ...  A name the model does not
+    know is reported and left out."""
+    import logging
+    stateMap = model.getStateNameMap()
+    if stateMap is None:
+        names = {str(i): i for i in range(model.getEmissionModel().getNumStates())}
+        size = len(names)
+        has, number = names.__contains__, names.__getitem__
+    else:
+        size = len(stateMap)
+        has, number = stateMap.has, stateMap.getMap
+    mask = np.zeros(size, dtype=np.int8)
+    for state in pdStates.split(","):
+        if not has(state):
+            logging.getLogger(__name__).warning(
+                "Posterior (or Emission) Distribution state %s not found in model" % state)
+        else:
+            mask[number(state)] = 1
+    return mask
 
 
 def bic(model, totalScore, totalDatapoints):
