@@ -280,6 +280,42 @@ int tehmm_segment_table_u8(int64_t T, int K, const uint8_t *data, int64_t n_seg,
 int tehmm_mask_table_u8(int64_t T, int K, const uint8_t *data, int KM, const uint8_t *maskdata, uint8_t *keep,
                         int32_t *run_full, uint8_t *out_data, int32_t *run_masked, int64_t *n_keep);
 
+/* ---- the step before that: the segments themselves (bin/segmentTracks.py:200-277) ------
+ * Cut rows of n_tables unsegmented uint8 tables, concatenated as tehmm_batch_create takes them: data
+ * [total][K], table t = rows [table_offsets[t], table_offsets[t + 1]) (table_offsets[0] = 0, ascending, no
+ * empty table).  Every table is a chain of its own, started at its first row; row i of a table opens a new
+ * segment when (fixLen > 0) the running segment holds fixLen rows -- nothing else is looked at then -- or
+ * (maxLen > 0) it holds maxLen rows, or row i differs from the segment's first row (comp_prev: from row
+ * i - 1) in a track with cut[k] != 0 or in more than thresh tracks; tracks with ignore[k] != 0 never count.
+ * Out: cuts = the table-relative offsets of every table's segments, ascending, table after table -- each
+ * table's list starts with its 0, so n_cuts[t] >= 1 is its number of segments and segment n covers rows
+ * [cuts[n], cuts[n + 1]) (the last one runs to the table's end); n_total = sum of n_cuts.  n_cuts and
+ * n_total are always written; when n_total > cap, cuts is left untouched and the call still returns
+ * TEHMM_OK (call again with a buffer of n_total).  stats_hist [K][K + 1] (NULL: not wanted): stats_hist[j][d]
+ * = number of cuts made by the data rule at which track j differed and d tracks differed in all (the
+ * reference's --stats: count[j] = sum_d hist[j][d], share[j] = sum_d hist[j][d] / d); cuts made by maxLen
+ * or fixLen add nothing, as in the reference.
+ * Checked before any device call: K <= 128 and total <= 2^31 - 1 (else TEHMM_ERR_UNSUPPORTED), thresh >= 0,
+ * the table offsets, NULL pointers (TEHMM_ERR_ARG).  The output equals the reference's chain integer for integer on
+ * every input; how the chain is cut into stripes and put together again: DESIGN.md section 5l. */
+int tehmm_segment_offsets_u8(int n_tables, const int64_t *table_offsets, int K, const uint8_t *data,
+                             const uint8_t *ignore, const uint8_t *cut, int thresh, int comp_prev, int64_t maxLen,
+                             int64_t fixLen, int64_t cap, int64_t *cuts, int64_t *n_cuts, int64_t *n_total,
+                             uint64_t *stats_hist);
+/* Rows per stripe of the speculative pass. */
+int64_t tehmm_segment_stripe_rows(void);
+/* Of the calling thread's last tehmm_segment_offsets_u8: stripes of the speculative pass (0 where no chain was
+ * needed: fixLen, or comp_prev without maxLen) and how many of them the link pass could not settle, so that the
+ * exact sequential walk took them (marked stripes and the stripes walked again behind them). */
+int tehmm_segment_last_counters(int64_t *stripes, int64_t *stripes_rewalked);
+/* Device time of the passes of the calling thread's last tehmm_segment_offsets_u8, measured with HIP events
+ * ("upload" and "download" include the host copies); returns the number of entries written. */
+int tehmm_segment_last_timing(int max_entries, const char **names, double *milliseconds);
+/* Host-side writer of the segment BED (segmentTracks.py:222-236): n lines "chrom\tstart\tend\tLABEL\n" with
+ * LABEL = first_label + i in lower-case hexadecimal without a prefix (Python's hex(x)[2:]). */
+int tehmm_write_segments_bed(const char *path, int append, const char *chrom, int64_t n, const int64_t *starts,
+                             const int64_t *ends, int64_t first_label);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

@@ -52,6 +52,12 @@ SIGNATURES = {
     "tehmm_model_get_params": (c_int, [vp, f64p, f64p, f64p]),
     "tehmm_segment_table_u8": (c_int, [c_i64, c_int, u8p, c_i64, i64p, u8p, f64p, u8p, f64p]),
     "tehmm_mask_table_u8": (c_int, [c_i64, c_int, u8p, c_int, u8p, u8p, i32p, u8p, i32p, i64p]),
+    "tehmm_segment_offsets_u8": (c_int, [c_int, i64p, c_int, u8p, u8p, u8p, c_int, c_int, c_i64, c_i64, c_i64, i64p,
+                                         i64p, i64p, ctypes.POINTER(ctypes.c_uint64)]),
+    "tehmm_segment_stripe_rows": (c_i64, []),
+    "tehmm_segment_last_counters": (c_int, [i64p, i64p]),
+    "tehmm_segment_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_write_segments_bed": (c_int, [ctypes.c_char_p, c_int, ctypes.c_char_p, c_i64, i64p, i64p, c_i64]),
     "tehmm_batch_get_interval_logprobs": (c_int, [vp, f64p]),
     "tehmm_batch_posterior_masksum": (c_int, [vp, f64p, c_i64, c_i64, f64p]),
     "tehmm_batch_map_decode": (c_int, [vp, f64p, f64p]),
