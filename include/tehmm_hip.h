@@ -316,6 +316,61 @@ int tehmm_segment_last_timing(int max_entries, const char **names, double *milli
 int tehmm_write_segments_bed(const char *path, int append, const char *chrom, int64_t n, const int64_t *starts,
                              const int64_t *ends, int64_t first_label);
 
+/* ---- the step after the path: judging a prediction against an annotation (bin/compareBedStates.py, ------
+ * bin/fitStateNames.py).  An interval list is n rows (chrom id, start, end, label), host
+ * arrays, uploaded by the call; chrom ids and labels are small integers the caller assigns (tehmm_amd/compare.py:
+ * by first appearance, ONE label table for both lists of a comparison), coordinates are full int64 (a list's total
+ * length must fit int64 too).  A list is valid when start < end, chrom ids never decrease, inside a chrom
+ * start[i] >= end[i - 1], and every label lies in [0, L); two lists are comparable when they cover the same bases
+ * (the reference's checkExactOverlap, which reads bed1 twice and so never looks at bed2's self-overlaps: both lists
+ * are checked here).  Checked before any device call, by every entry point below: NULL pointers, n >= 1, L >= 1
+ * (TEHMM_ERR_ARG); n <= 2^31 - 1 and L <= 2048 (TEHMM_ERR_UNSUPPORTED).
+ *
+ * tehmm_intervals_check: *which = 0 when both lists are valid and comparable, else 1 or 2 = the offending list and
+ * *where = the interval's index; the call returns TEHMM_OK either way (tehmm_last_error then holds a sentence).
+ * Order: validity of list 1, of list 2 (lowest index each), then the cover: the lowest interval of list 1 that starts
+ * (ends) a region -- no predecessor (successor) abuts it -- where list 2 starts (ends) none, then the same for list 2. */
+int tehmm_intervals_check(int64_t n1, const int32_t *chrom1, const int64_t *start1, const int64_t *end1,
+                          const int32_t *label1, int64_t n2, const int32_t *chrom2, const int64_t *start2,
+                          const int64_t *end2, const int32_t *label2, int L, int *which, int64_t *where);
+/* compareBaseLevel (compareBedStates.py:176-221) in one number per pair of labels: conf [L][L] host, conf[a][b] =
+ * bases labelled a in list 1 and b in list 2.  The reference's stats[s] = [FN, FP, TP] are row sum minus diagonal,
+ * column sum minus diagonal and diagonal; its confusion dict holds the non-zero cells as [name b][name a].
+ * first [L][L] host (NULL: not wanted): for every non-zero cell, (index in list 1 << 32 | index in list 2) of the two
+ * intervals whose overlap is the first of that cell along the lists -- where the reference's walk inserts the pair
+ * into its dicts, which is the order its later tie-breaks go by; -1 (all ones) in the other cells.
+ * Runs the check above first: TEHMM_ERR_ARG, with the offender named in tehmm_last_error, on lists that fail it. */
+int tehmm_compare_base(int64_t n1, const int32_t *chrom1, const int64_t *start1, const int64_t *end1,
+                       const int32_t *label1, int64_t n2, const int32_t *chrom2, const int64_t *start2,
+                       const int64_t *end2, const int32_t *label2, int L, int64_t *conf, int64_t *first);
+/* One side of compareIntervalsOneSided (compareBedStates.py:223-313).  For every true interval t, over the preds
+ * that overlap it, in list order: frac = (double)overlap / (double)(use_pred_len ? length of the pred : length of t);
+ * where the labels are equal best = max(best, frac) and total += frac (both from 0.0, IEEE fp64, this order); where
+ * frac >= threshold conf[label(pred)][label(t)] += 1.  t is a hit when (allow_multiple ? total : best) >= threshold.
+ * Out, by the label of t: n_hit / len_hit / n_miss / len_miss [L] (lengths in bases) and conf [L][L], all host;
+ * first [L][L] (NULL: not wanted) as in tehmm_compare_base, with (index of t << 32 | index of the pred).
+ * Same check and error as tehmm_compare_base. */
+int tehmm_compare_intervals(int64_t n_true, const int32_t *chrom_t, const int64_t *start_t, const int64_t *end_t,
+                            const int32_t *label_t, int64_t n_pred, const int32_t *chrom_p, const int64_t *start_p,
+                            const int64_t *end_p, const int32_t *label_p, int L, double threshold, int use_pred_len,
+                            int allow_multiple, int64_t *n_hit, int64_t *len_hit, int64_t *n_miss, int64_t *len_miss,
+                            int64_t *conf, int64_t *first);
+/* The merge of writeFittedBed (fitStateNames.py:241-268): labels go through lut [L] first (NULL: as they are; the
+ * values of lut are only compared, any int32 will do), then neighbours of equal chrom and mapped label with
+ * start[i] == end[i - 1] become one interval.  Only the labels are checked (TEHMM_ERR_ARG outside [0, L)); the list
+ * need not be valid.  On TEHMM_OK *n_out is written whatever cap is; when *n_out > cap the four outputs are left
+ * untouched and the call still returns TEHMM_OK (call again with buffers of *n_out).  On an error nothing is written. */
+int tehmm_merge_runs(int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, const int32_t *label,
+                     int L, const int32_t *lut, int64_t cap, int32_t *out_chrom, int64_t *out_start, int64_t *out_end,
+                     int32_t *out_label, int64_t *n_out);
+/* Device time of the passes of the calling thread's last call of the four above, as tehmm_segment_last_timing. */
+int tehmm_compare_last_timing(int max_entries, const char **names, double *milliseconds);
+/* The largest L whose matrices are accumulated in LDS, one copy per workgroup flushed once; above it every add is a
+ * 64-bit atomic on the global matrix. */
+int tehmm_compare_lds_labels(void);
+/* Intervals per workgroup of the run merge's count and scatter passes. */
+int64_t tehmm_compare_block_items(void);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

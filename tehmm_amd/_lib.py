@@ -58,6 +58,15 @@ SIGNATURES = {
     "tehmm_segment_last_counters": (c_int, [i64p, i64p]),
     "tehmm_segment_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_write_segments_bed": (c_int, [ctypes.c_char_p, c_int, ctypes.c_char_p, c_i64, i64p, i64p, c_i64]),
+    "tehmm_intervals_check": (c_int, [c_i64, i32p, i64p, i64p, i32p, c_i64, i32p, i64p, i64p, i32p, c_int,
+                                      ctypes.POINTER(c_int), i64p]),
+    "tehmm_compare_base": (c_int, [c_i64, i32p, i64p, i64p, i32p, c_i64, i32p, i64p, i64p, i32p, c_int, i64p, i64p]),
+    "tehmm_compare_intervals": (c_int, [c_i64, i32p, i64p, i64p, i32p, c_i64, i32p, i64p, i64p, i32p, c_int, c_dbl,
+                                        c_int, c_int, i64p, i64p, i64p, i64p, i64p, i64p]),
+    "tehmm_merge_runs": (c_int, [c_i64, i32p, i64p, i64p, i32p, c_int, i32p, c_i64, i32p, i64p, i64p, i32p, i64p]),
+    "tehmm_compare_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_compare_lds_labels": (c_int, []),
+    "tehmm_compare_block_items": (c_i64, []),
     "tehmm_batch_get_interval_logprobs": (c_int, [vp, f64p]),
     "tehmm_batch_posterior_masksum": (c_int, [vp, f64p, c_i64, c_i64, f64p]),
     "tehmm_batch_map_decode": (c_int, [vp, f64p, f64p]),
