@@ -385,6 +385,13 @@ int tehmm_batch_last_timing(tehmm_batch_t *batch, int max_entries, const char **
 /* Diagnostic builds only (-DTEHMM_STAMPS): per-wave cycle stamps of the last cooperative kernel,
  * [workgroup][wave][4] counters.  The product library returns TEHMM_ERR_UNSUPPORTED. */
 int tehmm_debug_read_stamps(unsigned long long *out, int n);
+/* Test-only: waits for the batch's streams and copies the index records of the fused posterior passes, as the last
+ * posterior evaluation or E-step left them, to out (host).  *n_words is their length in 64-bit words; when it exceeds
+ * max_words nothing is copied and the call still returns TEHMM_OK.  TEHMM_ERR_ARG when the batch holds no records.
+ * TEHMM_ROWINDEX_REF=1 in the environment of an evaluation (test-only as well) builds the records with the plain
+ * kernel that defines their layout; the default builder must produce the same bytes.  Records are cached per batch:
+ * the knob is read at every evaluation and records built by the other kernel are rebuilt. */
+int tehmm_debug_read_rowindex(tehmm_batch_t *batch, unsigned long long *out, int64_t max_words, int64_t *n_words);
 
 #ifdef __cplusplus
 }

@@ -97,6 +97,7 @@ SIGNATURES = {
     "tehmm_estep_batch": (c_int, [vp, vp, c_int, f64p, f64p, f64p, f64p]),
     "tehmm_batch_last_timing": (c_int, [vp, c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_debug_read_stamps": (c_int, [ctypes.POINTER(ctypes.c_uint64), c_int]),
+    "tehmm_debug_read_rowindex": (c_int, [vp, ctypes.POINTER(ctypes.c_uint64), c_i64, i64p]),
 }
 
 EVAL_VITERBI = 1

@@ -289,12 +289,13 @@ struct FusedOrder {
   int base[TEHMM_MAX_TRACKS];        // by processing slot: row base in the table the slot reads
   int cnt[TEHMM_MAX_TRACKS];         // by processing slot: rows of the track
 };
-// one thread per (tile, block, item in tile, step in block): FKW words.  Consecutive threads take consecutive STEPS of
-// one item -- SB observation rows, one contiguous run of the interval -- and the threads of the next item follow: the
-// reads are runs of SB rows and the writes runs of eight words per step (thread order (tile, step, item) read one
-// 12-byte row per 128-byte line: 4.2 ms per 100 Mb, ten times the bytes)
-__global__ __launch_bounds__(256) void k_fused_rowindex(IntervalTab iv, LaneGeom lg, FusedOrder fo, const uint8_t *obs,
-                                                        unsigned long long *rixx) {
+// The executable definition of the record layout (TEHMM_ROWINDEX_REF=1, test-only: the tests compare the records of
+// k_fused_rowindex with these byte for byte).  One thread per (tile, block, item in tile, step in block): FKW words.
+// Thread order (tile, block, item, step): a wave reads eight runs of SB observation rows L rows apart and writes, per
+// word, eight 64-byte runs 384 bytes apart; every thread pays three 64-bit divisions and a scalar load per entry of the
+// slot list.  2.3 ms per 100 Mb alone (profiles/r05_solo_kernel_stats.txt).
+__global__ __launch_bounds__(256) void k_fused_rowindex_ref(IntervalTab iv, LaneGeom lg, FusedOrder fo, const uint8_t *obs,
+                                                            unsigned long long *rixx) {
   const int E = fo.NB * fo.SB;
   const int64_t n = (int64_t)lg.n_groups * 4 * E * 16;
   const int per_blk = 16 * fo.SB;
@@ -325,6 +326,113 @@ __global__ __launch_bounds__(256) void k_fused_rowindex(IntervalTab iv, LaneGeom
         word |= (unsigned long long)(v & 0xffff) << (16 * b);
       }
       dst[(int64_t)w * 16] = word;
+    }
+  }
+}
+
+
+// The same records, 0.83 ms per 100 Mb alone = 4.5 GB of reads and writes at 5.4 TB/s (profiles/r05_solo_kernel_stats.txt;
+// DESIGN.md section 3).  A workgroup owns one 16-item tile and a run of `cps` chunks of RIX_CB = 4 blocks
+// (12 KB of records, the same 96 words per item whatever FKW), and per chunk
+//   1. reads each item's observation rows -- ONE contiguous run of the interval, the clamped head and tail steps
+//      re-use its first or last row -- as dwords, lanes along the bytes of an item, four items per wave, into LDS
+//      (the loads of chunk c + 1 are in flight while chunk c is translated);
+//   2. translates: thread (q, item) = (tid >> 4, tid & 15) builds the words q, q + 16, .. of its item from the staged
+//      bytes and the slot list, which sits in LDS as one (column | rows << 8, base | zero row << 16) pair per entry --
+//      two 16-byte reads per word; step and word number come from compile-time divisions by FKW;
+//   3. stores the 12 KB image, which is contiguous in rixx, with 16 bytes per lane.
+// No index is divided at run time and nothing is read outside the interval's own rows.
+#define TEHMM_RIX_CB 4
+#define TEHMM_RIX_STG 129        // dwords between the staged runs of two items (<= 128 used; odd: the 16 items of a
+                                 // half-wave read 16 different banks)
+template <int FKW>
+__global__ __launch_bounds__(256) void k_fused_rowindex(IntervalTab iv, LaneGeom lg, FusedOrder fo, const uint8_t *obs,
+                                                        unsigned long long *rixx, int cps) {
+  constexpr int SB = TEHMM_FUSED_BLKW / FKW, CB = TEHMM_RIX_CB, NS = CB * SB, STG = TEHMM_RIX_STG;
+  __shared__ fused_u4 s_img[CB * 192];
+  __shared__ fused_u4 s_slot[2 * TEHMM_FUSED_BLKW];       // entry i: dwords 2 i, 2 i + 1
+  __shared__ unsigned s_obs[16 * STG];
+  __shared__ long long s_a0[16], s_T[16], s_row0[16];     // per item: t0 - Wu, interval length, first row of the interval
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t tile = blockIdx.x;
+  const int KPW = fo.KP >> 2;
+  if (tid < 4 * TEHMM_FUSED_BLKW) {
+    unsigned x = 0, y = 0;
+    if (tid < fo.K) {
+      const int cnt = fo.cnt[tid] < 256 ? fo.cnt[tid] : 256;
+      x = (unsigned)fo.order[tid] | ((unsigned)cnt << 8);
+      y = ((unsigned)fo.base[tid] & 0xffffu) | ((unsigned)(tid < fo.n_glb ? fo.zero_glb : fo.zero_lds) << 16);
+    }
+    unsigned *sl = (unsigned *)s_slot;
+    sl[2 * tid] = x;
+    sl[2 * tid + 1] = y;
+  } else if (tid >= 128 && tid < 144) {
+    const int64_t item = tile * 16 + (tid - 128);
+    const bool valid = item < lg.n_items;
+    const int id = valid ? lg.item_iv[item] : 0;
+    s_a0[tid - 128] = (valid ? lg.item_t0[item] : 0) - fo.Wu;
+    s_T[tid - 128] = iv.len[id];
+    s_row0[tid - 128] = iv.pos0[id];
+  }
+  __syncthreads();
+  const int nchunk = (fo.NB + CB - 1) / CB;
+  const int c0 = blockIdx.y * cps, c1 = min(c0 + cps, nchunk);
+  auto clampT = [](int64_t t, int64_t T) { return T > 0 ? (t < 0 ? 0 : (t >= T ? T - 1 : t)) : 0; };
+  unsigned rr[4][2];
+  auto load = [&](int c) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int it = wv * 4 + j;
+      const int64_t a = s_a0[it] + (int64_t)c * NS, T = s_T[it];
+      const int64_t tf = clampT(a, T), tl = clampT(a + NS - 1, T);
+      const int nd = (int)(tl - tf + 1) * KPW;              // <= NS * KPW <= 128 (checked by the host)
+      const unsigned *src = (const unsigned *)obs + (s_row0[it] + tf) * KPW;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) rr[j][k] = lane + 64 * k < nd ? src[lane + 64 * k] : 0u;
+    }
+  };
+  const int i16 = tid & 15, q = tid >> 4;
+  const int64_t my_a0 = s_a0[i16], my_T = s_T[i16];
+  if (c0 < c1) load(c0);
+  for (int c = c0; c < c1; ++c) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) s_obs[(wv * 4 + j) * STG + lane + 64 * k] = rr[j][k];
+    }
+    __syncthreads();
+    if (c + 1 < c1) load(c + 1);
+    // step s of the chunk reads the staged row min(max(s, lo), hi) + off
+    const int64_t a = my_a0 + (int64_t)c * NS;
+    int lo = 0, hi = 0, off = 0;
+    if (my_T > 0) {
+      const int64_t big = 1 << 30, l = -a, h = my_T - 1 - a;
+      lo = (int)(l < -big ? -big : (l > big ? big : l));
+      hi = (int)(h < -big ? -big : (h > big ? big : h));
+      off = (int)(a - clampT(a, my_T));
+    }
+    const uint8_t *stage = (const uint8_t *)s_obs + i16 * (STG * 4);
+#pragma unroll
+    for (int jj = 0; jj < CB * TEHMM_FUSED_BLKW / 16; ++jj) {
+      const int sw = q + 16 * jj, step = sw / FKW, w = sw - step * FKW;
+      const uint8_t *row = stage + (min(max(step, lo), hi) + off) * fo.KP;
+      const fused_u4 sa = s_slot[2 * w], sb = s_slot[2 * w + 1];
+      const unsigned sx[4] = {sa.x, sa.z, sb.x, sb.z}, sy[4] = {sa.y, sa.w, sb.y, sb.w};
+      unsigned long long word = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const unsigned sym = row[sx[b] & 0xffu];
+        const unsigned v = sym < (sx[b] >> 8) ? (sy[b] & 0xffffu) + sym : sy[b] >> 16;
+        word |= (unsigned long long)(v & 0xffffu) << (16 * b);
+      }
+      ((unsigned long long *)s_img)[tid + 256 * jj] = word;
+    }
+    __syncthreads();
+    fused_u4 *dst = (fused_u4 *)rixx + (tile * fo.NB + (int64_t)c * CB) * 192;
+#pragma unroll
+    for (int jj = 0; jj < CB * 192 / 256; ++jj) {
+      const int p = tid + 256 * jj;
+      if (c * CB + p / 192 < fo.NB) dst[p] = s_img[p];
     }
   }
 }

@@ -352,6 +352,9 @@ struct LaneWork {
   DBuf<unsigned long long> rix;   // fused passes: observation rows as table-row index records (FusedTab::rixx)
   uint64_t rix_model = 0;
   int rix_L = 0, rix_Wu = 0;
+  size_t rix_words = 0;           // words of the current records
+  bool rix_ref = false;           // build them with k_fused_rowindex_ref (EvalKnobs::rowindex_ref of the current call)
+  bool rix_by_ref = false;        // ... and the kernel that built the current ones (part of the cache key)
   // forward / backward warm-up measured by k_fb_probe for (model, parameter version, item length)
   uint64_t wu_model = 0, wu_version = 0;
   int wu_L = 0, wu_val = 0;
@@ -1096,6 +1099,7 @@ int tehmm_batch_reset_cache(tehmm_batch_t *b) {
   b->lw.rix_model = 0;
   b->lw.rix_L = 0;
   b->lw.rix_Wu = 0;
+  b->lw.rix_words = 0;
   b->lw.wu_val = 0;
   return TEHMM_OK;
 }
@@ -1282,6 +1286,7 @@ struct EvalKnobs {
   bool soft_ties;       // TEHMM_SOFT_TIES=0: every rounding tie ends a piece of the quantised pass
   int emis_split;       // TEHMM_EMIS_SPLIT: three-wave emission + gain pass on (1) / off (0); -1: by batch size
   int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
+  bool rowindex_ref;    // TEHMM_ROWINDEX_REF=1 (test-only): index records by k_fused_rowindex_ref, the layout's definition
 };
 
 static EvalKnobs read_eval_knobs() {
@@ -1301,6 +1306,7 @@ static EvalKnobs read_eval_knobs() {
   k.soft_ties = num("TEHMM_SOFT_TIES", 1) != 0;
   k.emis_split = std::getenv("TEHMM_EMIS_SPLIT") ? (num("TEHMM_EMIS_SPLIT", 0) != 0 ? 1 : 0) : -1;
   k.defer = num("TEHMM_DEFER", -1);
+  k.rowindex_ref = num("TEHMM_ROWINDEX_REF", 0) != 0;
   return k;
 }
 
@@ -1846,9 +1852,12 @@ static void launch_fb_lane(tehmm_batch *b, const tehmm_model *m, const IntervalT
 // Index records of the fused passes (FusedTab::rixx): the track order of EmisStream's fixed schedule and, unless
 // the records of this (batch, model layout, item length, warm-up) exist already, k_fused_rowindex on `st`.
 // Depends on the observations only, so tehmm_eval_batch enqueues it ahead of the deferral behind the Viterbi
-// passes: the 3 ms of a first evaluation hide next to the emission-row kernel.
+// passes.  That does NOT hide it: in the split order (plan_lanes mode 3) the quantised Viterbi pass waits for
+// k_fused_fwd, which sits behind the record build on sP, so a first evaluation's build is on the step's critical path
+// ("The record build").  *built (optional): a build was enqueued by this call.
 template <int NT>
-static int fused_prepare(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, int Wu, hipStream_t st, FusedOrder &fo) {
+static int fused_prepare(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, int Wu, hipStream_t st, FusedOrder &fo,
+                         bool *built = nullptr) {
   LaneWork &lw = b->lw;
   const LaneGeom lg = lane_geom(lw);
   std::memset(&fo, 0, sizeof(fo));
@@ -1880,12 +1889,41 @@ static int fused_prepare(tehmm_batch *b, const tehmm_model *m, const IntervalTab
   }
   fo.SB = TEHMM_FUSED_BLKW / fo.FKW;
   fo.NB = (lw.L + 2 * Wu + fo.SB - 1) / fo.SB;
-  if (!lw.rix.p || lw.rix_model != m->uid || lw.rix_L != lw.L || lw.rix_Wu != Wu) {
+  if (built) *built = false;
+  if (!lw.rix.p || lw.rix_model != m->uid || lw.rix_L != lw.L || lw.rix_Wu != Wu || lw.rix_by_ref != lw.rix_ref) {
     const size_t words = (size_t)lw.n_groups * 4 * fo.NB * TEHMM_FUSED_BLKW * 16;
     lw.rix_model = 0;                                   // (the key is set once the records exist)
     HIPCHK(lw.rix.ensure(words + 16));
-    hipLaunchKernelGGL(k_fused_rowindex, dim3(grid_for((int64_t)lw.n_groups * 4 * fo.NB * fo.SB * 16, 256, 1 << 20)),
-                       dim3(256), 0, st, iv, lg, fo, (const uint8_t *)b->obs.p, lw.rix.p);
+    if (lw.rix_ref) {
+      hipLaunchKernelGGL(k_fused_rowindex_ref, dim3(grid_for((int64_t)lw.n_groups * 4 * fo.NB * fo.SB * 16, 256, 1 << 20)),
+                         dim3(256), 0, st, iv, lg, fo, (const uint8_t *)b->obs.p, lw.rix.p);
+    } else {
+      // A chunk of TEHMM_RIX_CB blocks stages CB * SB rows of KP / 4 dwords per item.  KP is the track count rounded
+      // up to 4 and the slot list holds every track (the fused routes stop at 78), so KP / 4 <= ceil(fo.K / 4) <= FKW
+      // and the run is at most CB * SB * FKW = CB * TEHMM_FUSED_BLKW dwords.  The test below cannot fail for a batch
+      // the fused routes accept; it keeps a caller that breaks the derivation from writing past the staging rows.
+      static_assert(TEHMM_RIX_CB * TEHMM_FUSED_BLKW <= TEHMM_RIX_STG - 1, "staged run of an item exceeds its LDS row");
+      if ((b->KP & 3) || b->KP / 4 > fo.FKW)
+        return fail(TEHMM_ERR_ARG, "fused_prepare: observation rows wider than the slot list (internal error)");
+      // tile x slice of the tile's chunks: enough workgroups to fill the device a few times over
+      const int tiles = lw.n_groups * 4, nchunk = (fo.NB + TEHMM_RIX_CB - 1) / TEHMM_RIX_CB;
+      const int want = std::min(nchunk, std::max(1, (32768 + tiles - 1) / std::max(1, tiles)));
+      const int cps = (nchunk + want - 1) / want, slices = (nchunk + cps - 1) / cps;
+      const dim3 grid((unsigned)tiles, (unsigned)slices);
+      switch (fo.FKW) {
+#define TEHMM_RIX_CASE(F_)                                                                                           \
+  case F_:                                                                                                          \
+    hipLaunchKernelGGL((k_fused_rowindex<F_>), grid, dim3(256), 0, st, iv, lg, fo, (const uint8_t *)b->obs.p,       \
+                       lw.rix.p, cps);                                                                              \
+    break;
+        TEHMM_RIX_CASE(1) TEHMM_RIX_CASE(2) TEHMM_RIX_CASE(3) TEHMM_RIX_CASE(4)
+        TEHMM_RIX_CASE(6) TEHMM_RIX_CASE(8) TEHMM_RIX_CASE(12) TEHMM_RIX_CASE(24)
+#undef TEHMM_RIX_CASE
+      }
+    }
+    lw.rix_words = words;
+    lw.rix_by_ref = lw.rix_ref;
+    if (built) *built = true;
     lw.rix_model = m->uid;
     lw.rix_L = lw.L;
     lw.rix_Wu = Wu;
@@ -3338,6 +3376,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   int rc = ensure_workspace(b, m, flags);
   if (rc) return rc;
   const EvalKnobs kn = read_eval_knobs();
+  b->lw.rix_ref = kn.rowindex_ref;
   EvalPlan p = plan_eval(m, b, flags, kn);
   if (p.vspec || p.fspec) {
     rc = spec_prepare(b, m, p.CS);
@@ -3378,6 +3417,21 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   if (p.dev_place) {
     rc = eval_place_setup(c);
     if (rc) return rc;
+  }
+  if (p.split_post) {
+    // The index records of a first evaluation go in FIRST, and the emission-row kernel waits for them: the quantised
+    // Viterbi pass waits for k_fused_fwd, which sits behind the record build on sP.  Started beside the emission-row
+    // kernel the build only gets the CUs that kernel leaves, whatever it takes alone, and the forward pass ends
+    // after the emission rows (measured: DESIGN.md section 3, "The record build"; the wait is inside the stage time
+    // emission_rows, the build itself in no stage of kernel_ms: forward_pass starts at ev[10], behind it).
+    FusedOrder fo_unused;
+    bool built = false;
+    nt_dispatch(m->NP, [&](auto nt) { rc = fused_prepare<nt>(b, m, c.iv, c.WuF, b->sP, fo_unused, &built); });
+    if (rc) return rc;
+    if (built) {
+      (void)hipEventRecord(b->evX[0], b->sP);
+      (void)hipStreamWaitEvent(b->sV, b->evX[0], 0);
+    }
   }
   rc = eval_emis_p0(c);
   if (rc) return rc;
@@ -4191,6 +4245,7 @@ static int launch_estep_reduce(tehmm_batch *b, const tehmm_model *m, const Inter
 static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, double *lp_out, int *dead_out, bool *done) {
   *done = false;
   const EvalKnobs kn = read_eval_knobs();
+  b->lw.rix_ref = kn.rowindex_ref;
   const int CS = kn.spec_chunk;
   if (!estep_fused_wanted(m, b, false, CS)) return TEHMM_OK;
   const int LS = lane_sub_size(CS, b->total, kn.lane_sub);
@@ -4774,4 +4829,19 @@ int tehmm_debug_read_stamps(unsigned long long *out, int n) {
   (void)out; (void)n;
   return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_debug_read_stamps: library built without -DTEHMM_STAMPS");
 #endif
+}
+
+// Diagnostic (tests): the index records of the fused passes as the batch holds them now.
+int tehmm_debug_read_rowindex(tehmm_batch_t *b, unsigned long long *out, int64_t max_words, int64_t *n_words) {
+  if (!b || !n_words || max_words < 0 || (max_words > 0 && !out))
+    return fail(TEHMM_ERR_ARG, "tehmm_debug_read_rowindex: bad argument");
+  if (!b->lw.rix.p || !b->lw.rix_model || !b->lw.rix_words)
+    return fail(TEHMM_ERR_ARG, "tehmm_debug_read_rowindex: the batch holds no index records");
+  if (b->sV) HIPCHK(hipStreamSynchronize(b->sV));
+  if (b->sP) HIPCHK(hipStreamSynchronize(b->sP));
+  if (b->sB) HIPCHK(hipStreamSynchronize(b->sB));
+  *n_words = (int64_t)b->lw.rix_words;
+  if (*n_words <= max_words)
+    HIPCHK(hipMemcpy(out, b->lw.rix.p, b->lw.rix_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return TEHMM_OK;
 }
