@@ -1170,25 +1170,29 @@ static int ensure_beta(tehmm_batch *b, const tehmm_model *m) {
   return TEHMM_OK;
 }
 
-// 64 <= N <= 128: the four-wave sequential kernels (k_*_wide); TEHMM_WIDE=0 selects the one-wave kernels
-static bool use_wide() {
-  const char *s = std::getenv("TEHMM_WIDE");
-  return !(s && std::atoi(s) == 0);
+// f(std::bool_constant<v>{}): a kernel family templated on a flag, launched for its run-time value
+template <class F>
+static void bool_dispatch(bool v, F &&f) {
+  if (v) f(std::bool_constant<true>{});
+  else f(std::bool_constant<false>{});
+}
+
+// 64 <= N <= 128: the four-wave sequential kernels (k_*_wide) where they apply; wide = false (TEHMM_WIDE=0) selects the
+// one-wave kernels
+static bool wide_kernels_apply(bool wide, const tehmm_model *m, const EmisTab &em) {
+  return wide && m->NP / 4 <= TEHMM_WIDE_QM && wide_lds_bytes(em.lds_rows, m->NP) <= 160 * 1024;
 }
 
 template <int SPL>
 static void launch_viterbi(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv,
-                           const EmisTab &em, bool ratio, hipStream_t st) {
-  if (use_wide() && m->NP / 4 <= TEHMM_WIDE_QM && wide_lds_bytes(em.lds_rows, m->NP) <= 160 * 1024) {
+                           const EmisTab &em, bool ratio, bool wide, hipStream_t st) {
+  if (wide_kernels_apply(wide, m, em)) {
     const size_t lds = wide_lds_bytes(em.lds_rows, m->NP);
-    allow_lds(k_viterbi_wide<true>, lds);
-    allow_lds(k_viterbi_wide<false>, lds);
-    if (ratio)
-      hipLaunchKernelGGL((k_viterbi_wide<true>), dim3(b->n), dim3(256), lds, st, iv, em, m->N, m->NP, m->lt.p, m->pi.p,
-                         (const double *)b->ratios.p, b->TBW, b->tb.p, b->last_state.p, b->vit_lp.p);
-    else
-      hipLaunchKernelGGL((k_viterbi_wide<false>), dim3(b->n), dim3(256), lds, st, iv, em, m->N, m->NP, m->lt.p, m->pi.p,
-                         (const double *)nullptr, b->TBW, b->tb.p, b->last_state.p, b->vit_lp.p);
+    bool_dispatch(ratio, [&](auto r) {
+      allow_lds(k_viterbi_wide<r>, lds);
+      hipLaunchKernelGGL((k_viterbi_wide<r>), dim3(b->n), dim3(256), lds, st, iv, em, m->N, m->NP, m->lt.p, m->pi.p,
+                         (const double *)(r ? b->ratios.p : nullptr), b->TBW, b->tb.p, b->last_state.p, b->vit_lp.p);
+    });
     return;
   }
   size_t lds = ((size_t)m->N * m->NP + (TEHMM_PB + 2) * 64 * SPL) * sizeof(double);
@@ -1206,8 +1210,8 @@ static void launch_viterbi(tehmm_batch *b, const tehmm_model *m, const IntervalT
 
 template <int SPL>
 static void launch_posterior(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv,
-                             const EmisTab &em, hipStream_t st, hipEvent_t mid) {
-  if (use_wide() && m->NP / 4 <= TEHMM_WIDE_QM && wide_lds_bytes(em.lds_rows, m->NP) <= 160 * 1024) {
+                             const EmisTab &em, bool wide, hipStream_t st, hipEvent_t mid) {
+  if (wide_kernels_apply(wide, m, em)) {
     const size_t lds = wide_lds_bytes(em.lds_rows, m->NP);
     allow_lds(k_forward_wide<false>, lds);
     allow_lds(k_backward_wide<false, true>, lds);
@@ -1272,10 +1276,13 @@ static int spec_chunk_size() {
   return std::max(64, (cs + 63) & ~63);
 }
 
-// The environment knobs of the N <= 128 evaluation and of the fused E-step, read once per call (tests flip them between
+#define TEHMM_ESTEP_SMALL_DEFAULT 40       // (where the split lies: see estep_build_groups)
+
+// The environment knobs of the N <= 128 evaluation and of the E-step, read once per call (tests flip them between
 // calls).  -1: not set (a negative TEHMM_DEFER counts as not set).
 struct EvalKnobs {
   int spec_chunk;       // TEHMM_SPEC_CHUNK: chunk length of the chunk-parallel passes (0: none)
+  bool spec_chunk_set;  // ... and whether it was set: unset, the 64-128 state Viterbi has a default of its own
   int lane_sub;         // TEHMM_LANE_SUB: item length of the lane = item passes (0: none; -1: by batch size)
   int lane_warmup;      // TEHMM_LANE_WARMUP: forward / backward warm-up (-1: probed)
   bool lane_probe;      // TEHMM_LANE_PROBE=0: warm-up 64 without the probe
@@ -1287,6 +1294,21 @@ struct EvalKnobs {
   int emis_split;       // TEHMM_EMIS_SPLIT: three-wave emission + gain pass on (1) / off (0); -1: by batch size
   int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
   bool rowindex_ref;    // TEHMM_ROWINDEX_REF=1 (test-only): index records by k_fused_rowindex_ref, the layout's definition
+  // 64 <= N <= 128
+  bool wide;            // TEHMM_WIDE=0: the one-wave sequential kernels instead of the four-wave ones (k_*_wide)
+  bool wide_cp;         // TEHMM_WIDE_CP=0: no chunk-parallel posterior
+  bool wide_vit;        // TEHMM_WIDE_VIT=0: no chunk-parallel exact Viterbi
+  int wide_sub;         // TEHMM_WIDE_SUB: item length of the item-parallel passes (a multiple of 32; -1: by batch size)
+  int wide_vit_warmup;  // TEHMM_WIDE_VIT_WARMUP: positions the quantised pass runs ahead of its chunk (<= chunk length)
+  double wide_tol;      // TEHMM_WIDE_TOL: link tolerance of the item-parallel passes, 1e-13 .. 1e-6
+  bool wide_head;       // TEHMM_WIDE_HEAD=0: no interval heads on a side stream next to the quantised pass
+  bool wide_poll;       // TEHMM_WIDE_POLL=0: the exact chain never follows the quantised pass while it runs
+  // E-step
+  int estep_wide;       // TEHMM_ESTEP_WIDE: item-parallel passes off (0), where the fused passes do not apply (1), everywhere (2)
+  bool estep_fused;     // TEHMM_ESTEP_FUSED=0: no fused E-step
+  int estep_small;      // TEHMM_ESTEP_SMALL: largest track, in rows, that takes the one-hot product
+  int wide_estep_sq;    // TEHMM_WIDE_ESTEP_SQ: position ranges per item tile in the reductions (0: by batch size)
+  bool wide_estep_serial;   // TEHMM_WIDE_ESTEP_SERIAL set: the three reductions one after the other, for profiling
 };
 
 static EvalKnobs read_eval_knobs() {
@@ -1296,6 +1318,7 @@ static EvalKnobs read_eval_knobs() {
   };
   EvalKnobs k;
   k.spec_chunk = spec_chunk_size();
+  k.spec_chunk_set = std::getenv("TEHMM_SPEC_CHUNK") != nullptr;
   k.lane_sub = std::getenv("TEHMM_LANE_SUB") ? std::max(0, num("TEHMM_LANE_SUB", 0)) : -1;
   k.lane_warmup = std::getenv("TEHMM_LANE_WARMUP") ? std::max(1, num("TEHMM_LANE_WARMUP", 1)) : -1;
   k.lane_probe = num("TEHMM_LANE_PROBE", 1) != 0;
@@ -1307,6 +1330,26 @@ static EvalKnobs read_eval_knobs() {
   k.emis_split = std::getenv("TEHMM_EMIS_SPLIT") ? (num("TEHMM_EMIS_SPLIT", 0) != 0 ? 1 : 0) : -1;
   k.defer = num("TEHMM_DEFER", -1);
   k.rowindex_ref = num("TEHMM_ROWINDEX_REF", 0) != 0;
+  k.wide = num("TEHMM_WIDE", 1) != 0;
+  k.wide_cp = num("TEHMM_WIDE_CP", 1) != 0;
+  k.wide_vit = num("TEHMM_WIDE_VIT", 1) != 0;
+  k.wide_sub = std::getenv("TEHMM_WIDE_SUB") ? std::max(32, (num("TEHMM_WIDE_SUB", 0) + 31) & ~31) : -1;
+  // (measured at 100 states, exact blocks of the chain per 480 kb: dense 3 300 at 64 and at 32 positions; sticky 0.995:
+  //  1 397 at 64, 1 392 at 32, 1 728 at 16 -- a chunk that has not converged only costs the chain one 16-position block)
+  k.wide_vit_warmup = std::max(0, num("TEHMM_WIDE_VIT_WARMUP", 32));
+  // link tolerance (Hilbert distance between the vector an item arrives with and the one its neighbour left): 1e-8 -- the
+  // alpha' rows between the passes are floats (6e-8 each, posteriors observed at 1.2e-7 of the reference, bar 1e-6), and an
+  // item's error is the link's distance at its first position, smaller further in.  Round 3 asked for 1e-10: twice the
+  // warm-up at 100 states for nothing a float row can show.
+  k.wide_tol = 1e-8;
+  if (const char *ts = std::getenv("TEHMM_WIDE_TOL")) k.wide_tol = std::min(1e-6, std::max(1e-13, std::atof(ts)));
+  k.wide_head = num("TEHMM_WIDE_HEAD", 1) != 0;
+  k.wide_poll = num("TEHMM_WIDE_POLL", 1) != 0;
+  k.estep_wide = num("TEHMM_ESTEP_WIDE", 1);
+  k.estep_fused = num("TEHMM_ESTEP_FUSED", 1) != 0;
+  k.estep_small = num("TEHMM_ESTEP_SMALL", TEHMM_ESTEP_SMALL_DEFAULT);
+  k.wide_estep_sq = num("TEHMM_WIDE_ESTEP_SQ", 0);
+  k.wide_estep_serial = std::getenv("TEHMM_WIDE_ESTEP_SERIAL") != nullptr;
   return k;
 }
 
@@ -2075,76 +2118,56 @@ static void nt_dispatch(int NP, F &&f) {
 
 
 // ---- chunk-parallel posterior for 64 <= N <= 128 (tehmm_wide.hip.h) ---------------------------------------------
-template <int NPW>
+// Padded widths of the item-parallel passes, for nt_dispatch_of.  Two lists: the posterior only runs at 64 <= N <= 128
+// (over all eight it would instantiate k_wide_bwd<16..64, false>, which nothing launches); the E-step and the emission
+// rows take every N <= 128.
+#define TEHMM_WIDE_POST_WIDTHS 80, 96, 112, 128
+#define TEHMM_WIDE_ESTEP_WIDTHS 16, 32, 48, 64, 80, 96, 112, 128
+template <int... NPWs>
+static int wide_npw(int N) {          // the narrowest width of the list that holds N states (0: none does)
+  int npw = 0;
+  (void)((N <= NPWs && (npw = NPWs, true)) || ...);
+  return npw;
+}
+
+constexpr int kWideWuMax = 1024;      // the longest warm-up the passes try
+
+static LaneGeom wide_lane_geom(const WideWork &w) {
+  LaneGeom lg;
+  lg.item_iv = w.item_iv.p; lg.item_t0 = w.item_t0.p; lg.ifirst = w.ifirst.p;
+  lg.n_items = w.n_items; lg.n_groups = w.n_groups; lg.L = w.L;
+  return lg;
+}
+
+// ESTEP (tehmm_wide_estep.hip.h): the backward pass leaves gamma / wz rows instead of posteriors
+template <int NPW, bool ESTEP>
 static void launch_wide_passes(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const LaneGeom &lg, int Wu,
                                hipStream_t st, hipEvent_t mid) {
   WideWork &w = b->ww;
   const size_t lds = WideGeom<NPW>::FRAG_BYTES;
   allow_lds(k_wide_fwd<NPW>, lds);
-  allow_lds(k_wide_bwd<NPW>, lds);
+  allow_lds(k_wide_bwd<NPW, ESTEP>, lds);
   const dim3 grid((unsigned)std::max(1, w.n_groups));
   hipLaunchKernelGGL((k_wide_fwd<NPW>), grid, dim3(256), lds, st, iv, lg, m->N, m->NP, Wu, (const double *)m->A.p,
                      (const double *)m->pi.p, (const double *)w.E.p, (const double *)w.ms.p, w.AL.p, w.pre_f.p, w.end_f.p,
                      w.SL.p);
   (void)hipEventRecord(mid, st);
-  hipLaunchKernelGGL((k_wide_bwd<NPW>), grid, dim3(256), lds, st, iv, lg, m->N, m->NP, Wu, (const double *)m->A.p,
-                     (const double *)w.E.p, (const float *)w.AL.p, b->post.p, w.pre_b.p, w.end_b.p);
+  hipLaunchKernelGGL((k_wide_bwd<NPW, ESTEP>), grid, dim3(256), lds, st, iv, lg, m->N, m->NP, Wu, (const double *)m->A.p,
+                     (const double *)w.E.p, (const float *)w.AL.p, ESTEP ? (double *)nullptr : b->post.p, w.pre_b.p, w.end_b.p,
+                     ESTEP ? w.GAM.p : (float *)nullptr, ESTEP ? w.WZ.p : (float *)nullptr);
 }
 
-// the E-step form (tehmm_wide_estep.hip.h): the backward pass leaves gamma / wz rows instead of posteriors
-template <int NPW>
-static void launch_wide_passes_estep(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const LaneGeom &lg, int Wu,
-                                     hipStream_t st, hipEvent_t mid) {
+// One attempt of the item-parallel passes with warm-up Wu, enqueued on st: passes (estep: the E-step form of the
+// backward pass), link checks, and the flags (impossible rows, failed links) on their way to pinned host memory.
+static int wide_post_attempt(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EvalKnobs &kn, int Wu, hipStream_t st,
+                             hipEvent_t mid, bool estep) {
   WideWork &w = b->ww;
-  const size_t lds = WideGeom<NPW>::FRAG_BYTES;
-  allow_lds(k_wide_fwd<NPW>, lds);
-  allow_lds(k_wide_bwd<NPW, true>, lds);
-  const dim3 grid((unsigned)std::max(1, w.n_groups));
-  hipLaunchKernelGGL((k_wide_fwd<NPW>), grid, dim3(256), lds, st, iv, lg, m->N, m->NP, Wu, (const double *)m->A.p,
-                     (const double *)m->pi.p, (const double *)w.E.p, (const double *)w.ms.p, w.AL.p, w.pre_f.p, w.end_f.p,
-                     w.SL.p);
-  (void)hipEventRecord(mid, st);
-  hipLaunchKernelGGL((k_wide_bwd<NPW, true>), grid, dim3(256), lds, st, iv, lg, m->N, m->NP, Wu, (const double *)m->A.p,
-                     (const double *)w.E.p, (const float *)w.AL.p, (double *)nullptr, w.pre_b.p, w.end_b.p, w.GAM.p, w.WZ.p);
-}
-
-// One attempt of the chunk-parallel posterior with warm-up Wu, enqueued on st: passes, link checks, and the flags
-// (impossible rows, failed links) on their way to pinned host memory.
-static int wide_post_attempt(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, int Wu, hipStream_t st, hipEvent_t mid,
-                             bool estep = false) {
-  WideWork &w = b->ww;
-  LaneGeom lg;
-  lg.item_iv = w.item_iv.p; lg.item_t0 = w.item_t0.p; lg.ifirst = w.ifirst.p;
-  lg.n_items = w.n_items; lg.n_groups = w.n_groups; lg.L = w.L;
-  const int NPW = w.NPW;
-  if (estep) {
-    switch (NPW) {
-      case 16: launch_wide_passes_estep<16>(b, m, iv, lg, Wu, st, mid); break;
-      case 32: launch_wide_passes_estep<32>(b, m, iv, lg, Wu, st, mid); break;
-      case 48: launch_wide_passes_estep<48>(b, m, iv, lg, Wu, st, mid); break;
-      case 64: launch_wide_passes_estep<64>(b, m, iv, lg, Wu, st, mid); break;
-      case 80: launch_wide_passes_estep<80>(b, m, iv, lg, Wu, st, mid); break;
-      case 96: launch_wide_passes_estep<96>(b, m, iv, lg, Wu, st, mid); break;
-      case 112: launch_wide_passes_estep<112>(b, m, iv, lg, Wu, st, mid); break;
-      default: launch_wide_passes_estep<128>(b, m, iv, lg, Wu, st, mid); break;
-    }
-  } else
-  switch (NPW) {
-    case 80: launch_wide_passes<80>(b, m, iv, lg, Wu, st, mid); break;
-    case 96: launch_wide_passes<96>(b, m, iv, lg, Wu, st, mid); break;
-    case 112: launch_wide_passes<112>(b, m, iv, lg, Wu, st, mid); break;
-    default: launch_wide_passes<128>(b, m, iv, lg, Wu, st, mid); break;
-  }
-  // link tolerance (Hilbert distance between the vector an item arrives with and the one its neighbour left): 1e-8 -- the
-  // alpha' rows between the passes are floats (6e-8 each, posteriors observed at 1.2e-7 of the reference, bar 1e-6), and an
-  // item's error is the link's distance at its first position, smaller further in.  Round 3 asked for 1e-10: twice the
-  // warm-up at 100 states for nothing a float row can show.
-  double tol = 1e-8;
-  if (const char *ts = std::getenv("TEHMM_WIDE_TOL")) tol = std::min(1e-6, std::max(1e-13, std::atof(ts)));
-  (void)estep;
-  hipLaunchKernelGGL(k_wide_links, dim3((w.n_items + 255) / 256), dim3(256), 0, st, iv, lg, m->N, NPW,
+  const LaneGeom lg = wide_lane_geom(w);
+  if (estep) nt_dispatch_of<TEHMM_WIDE_ESTEP_WIDTHS>(w.NPW, [&](auto npw) { launch_wide_passes<npw, true>(b, m, iv, lg, Wu, st, mid); });
+  else nt_dispatch_of<TEHMM_WIDE_POST_WIDTHS>(w.NPW, [&](auto npw) { launch_wide_passes<npw, false>(b, m, iv, lg, Wu, st, mid); });
+  hipLaunchKernelGGL(k_wide_links, dim3((w.n_items + 255) / 256), dim3(256), 0, st, iv, lg, m->N, w.NPW,
                      (const double *)w.pre_f.p, (const double *)w.end_f.p, (const double *)w.pre_b.p,
-                     (const double *)w.end_b.p, w.lr.p, w.flags.p, tol);
+                     (const double *)w.end_b.p, w.lr.p, w.flags.p, kn.wide_tol);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(w.h_flags, w.flags.p, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
   w.pp_Wu = Wu;
@@ -2152,36 +2175,52 @@ static int wide_post_attempt(tehmm_batch *b, const tehmm_model *m, const Interva
   return TEHMM_OK;
 }
 
-// The attempt's verdict (waits for st): links that do not verify double the warm-up and run again, up to 1024
-// positions.  *done = true: posteriors and forward log-likelihoods of the batch are in place; false: the caller runs
-// the sequential kernels (a link that does not verify within the longest warm-up, impossible rows).
-static int posterior_wide_finish(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, hipStream_t st, hipEvent_t mid,
-                                 bool *done) {
+// What the E-step wants to see of the verdict loop (the posterior passes nullptr)
+struct WideRetries {
+  hipEvent_t ev_attempt;    // recorded before every re-attempt: the forward stage time is that of the last attempt
+  hipEvent_t ev_verified;   // recorded when the links have verified, before the log-likelihoods
+  int attempts;             // attempts so far, the one the caller enqueued included
+};
+
+// Takes the attempt enqueued on st to its verdict (waits for st): links that do not verify double the warm-up and run
+// again, up to 1024 positions.  *done = true: the links verified with warm-up w.wu_ok, the passes' results and the forward
+// log-likelihoods of the batch are in place; false: the caller falls back to the sequential kernels (a link that does
+// not verify within the longest warm-up, impossible rows).
+static int wide_verdict(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EvalKnobs &kn, hipStream_t st, hipEvent_t mid,
+                        bool estep, WideRetries *re, bool *done) {
   *done = false;
   WideWork &w = b->ww;
-  if (!w.pp_active) return TEHMM_OK;
-  w.pp_active = false;
-  constexpr int kWuMax = 1024;
   for (;;) {
+    w.pp_active = false;
     HIPCHK(hipStreamSynchronize(st));
     const int Wu = w.pp_Wu;
     if (w.h_flags[0] > 0) return TEHMM_OK;             // impossible rows: the sequential kernels own their semantics
     if (w.h_flags[1] == 0) break;
-    if (Wu >= kWuMax) return TEHMM_OK;                 // does not forget: sequential kernels
+    if (Wu >= kWideWuMax) return TEHMM_OK;             // does not forget: sequential kernels
     HIPCHK(hipMemsetAsync(w.flags.p, 0, 4 * sizeof(int), st));
-    if (int rc = wide_post_attempt(b, m, iv, std::min(kWuMax, 2 * Wu), st, mid)) return rc;
-    w.pp_active = false;
+    if (re) {
+      (void)hipEventRecord(re->ev_attempt, st);
+      ++re->attempts;
+    }
+    if (int rc = wide_post_attempt(b, m, iv, kn, std::min(kWideWuMax, 2 * Wu), st, mid, estep)) return rc;
   }
   w.wu_ok = w.pp_Wu;
   w.wu_model = m->uid;
   w.wu_version = m->version;
-  LaneGeom lg;
-  lg.item_iv = w.item_iv.p; lg.item_t0 = w.item_t0.p; lg.ifirst = w.ifirst.p;
-  lg.n_items = w.n_items; lg.n_groups = w.n_groups; lg.L = w.L;
-  hipLaunchKernelGGL(k_wide_loglik, dim3((b->n + 3) / 4), dim3(256), 0, st, iv, lg, m->N, w.NPW, (const double *)w.end_f.p,
-                     (const double *)w.SL.p, (const double *)w.lr.p, b->fwd_lp.p);
+  if (re) (void)hipEventRecord(re->ev_verified, st);
+  hipLaunchKernelGGL(k_wide_loglik, dim3((b->n + 3) / 4), dim3(256), 0, st, iv, wide_lane_geom(w), m->N, w.NPW,
+                     (const double *)w.end_f.p, (const double *)w.SL.p, (const double *)w.lr.p, b->fwd_lp.p);
   *done = true;
   return TEHMM_OK;
+}
+
+// The verdict of the attempt posterior_wide_cp enqueued.  *done = true: posteriors and forward log-likelihoods of the
+// batch are in place; false: the caller runs the sequential kernels.
+static int posterior_wide_finish(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EvalKnobs &kn, hipStream_t st,
+                                 hipEvent_t mid, bool *done) {
+  *done = false;
+  if (!b->ww.pp_active) return TEHMM_OK;
+  return wide_verdict(b, m, iv, kn, st, mid, false, nullptr, done);
 }
 
 // emission rows of the item-parallel passes in the tile layout (k_wide_emis_tile): mode 0 tables, 1 from the log rows
@@ -2228,16 +2267,7 @@ static void launch_wide_emis_npw(tehmm_batch *b, const tehmm_model *m, const Int
 }
 static void launch_wide_emis(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em, const LaneGeom &lg,
                              int mode, const double *log_rows, hipStream_t st) {
-  switch (b->ww.NPW) {
-    case 16: launch_wide_emis_npw<16>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 32: launch_wide_emis_npw<32>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 48: launch_wide_emis_npw<48>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 64: launch_wide_emis_npw<64>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 80: launch_wide_emis_npw<80>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 96: launch_wide_emis_npw<96>(b, m, iv, em, lg, mode, log_rows, st); break;
-    case 112: launch_wide_emis_npw<112>(b, m, iv, em, lg, mode, log_rows, st); break;
-    default: launch_wide_emis_npw<128>(b, m, iv, em, lg, mode, log_rows, st); break;
-  }
+  nt_dispatch_of<TEHMM_WIDE_ESTEP_WIDTHS>(b->ww.NPW, [&](auto npw) { launch_wide_emis_npw<npw>(b, m, iv, em, lg, mode, log_rows, st); });
 }
 
 // Item geometry and workspaces of the item-parallel passes for (NPW, L); *fits = false: not enough device memory
@@ -2286,42 +2316,42 @@ static int wide_geometry(tehmm_batch *b, int NPW, int L, bool *fits) {
   return TEHMM_OK;
 }
 
+// item length: enough items to give every SIMD a tile (1024 tiles of 16 items), 64 <= L <= 512, multiple of 32 --
+// or TEHMM_WIDE_SUB
+static int wide_item_length(const tehmm_batch *b, const EvalKnobs &kn) {
+  if (kn.wide_sub > 0) return kn.wide_sub;
+  return (int)std::min<int64_t>(512, std::max<int64_t>(64, (b->total / (16 * 1024) + 31) & ~31));
+}
+
+// warm-up of the first attempt: 64 positions to begin with (it may exceed the item length: the passes read the emission
+// rows of the interval, not of the item), or TEHMM_LANE_WARMUP, or what the last run with this model needed.  The
+// posterior asks for the same parameters (match_version); the E-step for the same model handle only: its parameters
+// move a little per iteration, and the links are verified whatever the guess.
+static int wide_first_warmup(const WideWork &w, const tehmm_model *m, const EvalKnobs &kn, bool match_version) {
+  if (kn.lane_warmup > 0) return std::min(kWideWuMax, kn.lane_warmup);
+  if (w.wu_ok > 0 && w.wu_model == m->uid && (!match_version || w.wu_version == m->version)) return w.wu_ok;
+  return 64;
+}
+
 // Chunk-parallel posterior for 64 <= N <= 128: geometry, emission rows and the first attempt are ENQUEUED here
 // (*pending = true; nothing enqueued otherwise: short batches, TEHMM_WIDE_CP=0); posterior_wide_finish delivers the
 // verdict, so the exact Viterbi of the same evaluation can be enqueued in between and share the GPU with the passes.
-static int posterior_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em, hipStream_t st,
-                             hipEvent_t mid, bool *pending, const double *log_rows = nullptr) {
+static int posterior_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em, const EvalKnobs &kn,
+                             hipStream_t st, hipEvent_t mid, bool *pending, const double *log_rows) {
   *pending = false;
-  const char *ws = std::getenv("TEHMM_WIDE_CP");
-  if (ws && std::atoi(ws) == 0) return TEHMM_OK;
+  if (!kn.wide_cp) return TEHMM_OK;
   if (m->N < 64 || m->N > 128 || b->total < 4096) return TEHMM_OK;
-  static const int sizes[] = {80, 96, 112, 128};
-  int NPW = 128;
-  for (int sz : sizes)
-    if (m->N <= sz) { NPW = sz; break; }
   WideWork &w = b->ww;
   if (!w.h_flags) HIPCHK(hipHostMalloc((void **)&w.h_flags, 64, hipHostMallocDefault));
-  // item length: enough items to give every SIMD a tile (1024 tiles of 16 items), 64 <= L <= 512, multiple of 32
-  int L = (int)std::min<int64_t>(512, std::max<int64_t>(64, (b->total / (16 * 1024) + 31) & ~31));
-  if (const char *ls = std::getenv("TEHMM_WIDE_SUB")) L = std::max(32, (std::atoi(ls) + 31) & ~31);
   {
     bool fits = true;
-    if (int rcg = wide_geometry(b, NPW, L, &fits)) return rcg;
+    if (int rcg = wide_geometry(b, wide_npw<TEHMM_WIDE_POST_WIDTHS>(m->N), wide_item_length(b, kn), &fits)) return rcg;
     if (!fits) return TEHMM_OK;
   }
-  LaneGeom lg;
-  lg.item_iv = w.item_iv.p; lg.item_t0 = w.item_t0.p; lg.ifirst = w.ifirst.p;
-  lg.n_items = w.n_items; lg.n_groups = w.n_groups; lg.L = L;
   HIPCHK(hipMemsetAsync(w.flags.p, 0, 4 * sizeof(int), st));
   // (log_rows: the exact Viterbi of this evaluation has the log rows already (k_wide_logrows): no second gather)
-  launch_wide_emis(b, m, iv, em, lg, log_rows ? 1 : 0, log_rows, st);
-  // warm-up: 64 positions to begin with (it may exceed the item length: the passes read the emission rows of the
-  // interval, not of the item), or what the last evaluation with this model needed
-  constexpr int kWuMax = 1024;
-  int Wu = 64;
-  if (const char *wus = std::getenv("TEHMM_LANE_WARMUP")) Wu = std::min(kWuMax, std::max(1, std::atoi(wus)));
-  else if (w.wu_ok > 0 && w.wu_model == m->uid && w.wu_version == m->version) Wu = w.wu_ok;
-  if (int rc = wide_post_attempt(b, m, iv, Wu, st, mid)) return rc;
+  launch_wide_emis(b, m, iv, em, wide_lane_geom(w), log_rows ? 1 : 0, log_rows, st);
+  if (int rc = wide_post_attempt(b, m, iv, kn, wide_first_warmup(w, m, kn, true), st, mid, false)) return rc;
   *pending = true;
   return TEHMM_OK;
 }
@@ -2330,23 +2360,16 @@ static int posterior_wide_cp(tehmm_batch *b, const tehmm_model *m, const Interva
 // ---- chunk-parallel exact Viterbi for 64 <= N <= 128 (tehmm_wide.hip.h) -------------------------------------------
 // *done = true: traceback bytes, last states and scores of the batch are in place (the generic traceback follows);
 // false: the caller runs the sequential kernels
-static int wide_vit_warmup(int CS) {    // positions the quantised pass runs ahead of its chunk (<= chunk length)
-  const char *s = std::getenv("TEHMM_WIDE_VIT_WARMUP");
-  // (measured at 100 states, exact blocks of the chain per 480 kb: dense 3 300 at 64 and at 32 positions; sticky 0.995:
-  //  1 397 at 64, 1 392 at 32, 1 728 at 16 -- a chunk that has not converged only costs the chain one 16-position block)
-  return std::min(CS, std::max(0, s ? std::atoi(s) : 32));
-}
 static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em, bool ratio,
-                           hipStream_t st, hipEvent_t ev_spec, bool *done) {
+                           const EvalKnobs &kn, hipStream_t st, hipEvent_t ev_spec, bool *done) {
   *done = false;
-  const char *ws = std::getenv("TEHMM_WIDE_VIT");
-  if (ws && std::atoi(ws) == 0) return TEHMM_OK;
+  if (!kn.wide_vit) return TEHMM_OK;
   // chunks of 256 positions unless TEHMM_SPEC_CHUNK says otherwise: a chunk that crosses into the next binade is walked
   // exactly up to the crossing (half a chunk on average, seven crossings per 100 kb interval), an interval's first
   // chunk always (measured, 2 Mb in 20 intervals at 100 states: 1024 -> 55 ms, 512 -> 38, 256 -> 32, 128 -> 31)
-  const int CS = std::getenv("TEHMM_SPEC_CHUNK") ? spec_chunk_size() : 256;
+  const int CS = kn.spec_chunk_set ? kn.spec_chunk : 256;
   if (m->N < 64 || m->N > 128 || CS < 64 || b->total < 2 * (int64_t)CS) return TEHMM_OK;
-  if (use_wide() == false || !(m->NP / 4 <= TEHMM_WIDE_QM && wide_lds_bytes(em.lds_rows, m->NP) <= 160 * 1024)) return TEHMM_OK;
+  if (!wide_kernels_apply(kn.wide, m, em)) return TEHMM_OK;
   int rc = spec_prepare(b, m, CS);
   if (rc) return rc;
   SpecWork &sw = b->sw;
@@ -2387,30 +2410,13 @@ static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalT
     HIPCHK(w.wk_c.ensure(w.h_wkc.size() + 8));
     HIPCHK(w.wk_e.ensure(w.h_wke.size() + 8));
     HIPCHK(hipMemcpyAsync(w.wk_c.p, w.h_wkc.data(), w.h_wkc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    const char *pf = std::getenv("TEHMM_WIDE_P0F");
-    if (!(pf && std::atoi(pf) == 0)) {
-      // packed floats (k_vit_wide_gain): the gains only place the binades
-      const size_t ldsg = (size_t)m->N * 64 * sizeof(float2);
-      if (ratio) {
-        allow_lds(k_vit_wide_gain<true>, ldsg);
-        hipLaunchKernelGGL((k_vit_wide_gain<true>), dim3(nwg), dim3(512), ldsg, st, iv, vc, m->N, m->NP, (const double *)m->lt.p,
-                           (const double *)w.BL.p, (const double *)b->ratios.p);
-      } else {
-        allow_lds(k_vit_wide_gain<false>, ldsg);
-        hipLaunchKernelGGL((k_vit_wide_gain<false>), dim3(nwg), dim3(512), ldsg, st, iv, vc, m->N, m->NP, (const double *)m->lt.p,
-                           (const double *)w.BL.p, (const double *)nullptr);
-      }
-    } else if (ratio) {
-      allow_lds(k_vit_wide_spec<false, true>, lds);
-      hipLaunchKernelGGL((k_vit_wide_spec<false, true>), dim3(nwg), dim3(512), lds, st, iv, vc, m->N, m->NP,
-                         (const double *)m->lt.p, (const double *)w.BL.p, (const double *)b->ratios.p,
-                         (const int *)w.wk_c.p, (const int *)w.wk_e.p, b->TBW, b->tb.p, w.tb2.p, w.rows2.p, wide_vit_warmup(CS), w.pre.p);
-    } else {
-      allow_lds(k_vit_wide_spec<false, false>, lds);
-      hipLaunchKernelGGL((k_vit_wide_spec<false, false>), dim3(nwg), dim3(512), lds, st, iv, vc, m->N, m->NP,
-                         (const double *)m->lt.p, (const double *)w.BL.p, (const double *)nullptr,
-                         (const int *)w.wk_c.p, (const int *)w.wk_e.p, b->TBW, b->tb.p, w.tb2.p, w.rows2.p, wide_vit_warmup(CS), w.pre.p);
-    }
+    // packed floats (k_vit_wide_gain): the gains only place the binades
+    const size_t ldsg = (size_t)m->N * 64 * sizeof(float2);
+    bool_dispatch(ratio, [&](auto r) {
+      allow_lds(k_vit_wide_gain<r>, ldsg);
+      hipLaunchKernelGGL((k_vit_wide_gain<r>), dim3(nwg), dim3(512), ldsg, st, iv, vc, m->N, m->NP, (const double *)m->lt.p,
+                         (const double *)w.BL.p, (const double *)(r ? b->ratios.p : nullptr));
+    });
     w.h_gain.resize((size_t)nc);
     HIPCHK(hipMemcpyAsync(w.h_gain.data(), sw.gain.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2438,12 +2444,10 @@ static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalT
   const int nwg2 = (int)w.h_wke.size();
   // every interval's head -- what lies before its first speculated chunk -- is walked by the exact chain on a side
   // stream WHILE the quantised pass runs (phase 1 of k_vit_wide_fix); the chain proper resumes behind it (phase 2)
-  const char *hds = std::getenv("TEHMM_WIDE_HEAD");
-  const bool head = !(hds && std::atoi(hds) == 0) && nwg2 > 0;
+  const bool head = kn.wide_head && nwg2 > 0;
   // ... and with few enough intervals that their workgroups cannot keep the pass off the GPU, phase 2 follows the pass
   // WHILE it runs, waiting for each chunk's ready flag
-  const char *pls = std::getenv("TEHMM_WIDE_POLL");
-  const bool poll = head && b->n <= 64 && !(pls && std::atoi(pls) == 0);
+  const bool poll = head && b->n <= 64 && kn.wide_poll;
   // polls (~2.7 us each) a chain may spend waiting: the pass needs ~1.4 us per chunk with the GPU to itself, allow tenfold
   const int spin_limit = (int)std::min<int64_t>(1 << 20, std::max<int64_t>(1 << 13, (int64_t)nc * 6));
   if (head) {
@@ -2467,21 +2471,14 @@ static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalT
   HIPCHK(hipMemsetAsync(w.ready.p, 0, ((size_t)nc + 1) * sizeof(int), st));
   const size_t ldsf = wide_lds_bytes(em.lds_rows, m->NP);
   auto launch_chain = [&](int phase, hipStream_t s2) {
-    if (ratio) {
-      allow_lds(k_vit_wide_fix<true>, ldsf);
-      hipLaunchKernelGGL((k_vit_wide_fix<true>), dim3(b->n), dim3(256), ldsf, s2, iv, em, vc, m->N, m->NP, (const double *)m->lt.p,
-                         (const double *)m->pi.p, (const double *)b->ratios.p, b->TBW, b->tb.p, b->last_state.p, b->vit_lp.p,
-                         sw.stats.p, (const double *)w.rows2.p, (const double *)w.BL.p, w.sel_from.p, w.sel_hyp.p,
+    bool_dispatch(ratio, [&](auto r) {
+      allow_lds(k_vit_wide_fix<r>, ldsf);
+      hipLaunchKernelGGL((k_vit_wide_fix<r>), dim3(b->n), dim3(256), ldsf, s2, iv, em, vc, m->N, m->NP, (const double *)m->lt.p,
+                         (const double *)m->pi.p, (const double *)(r ? b->ratios.p : nullptr), b->TBW, b->tb.p, b->last_state.p,
+                         b->vit_lp.p, sw.stats.p, (const double *)w.rows2.p, (const double *)w.BL.p, w.sel_from.p, w.sel_hyp.p,
                          (const double *)w.pre.p, phase, (const int64_t *)w.hstop.p, w.hvec.p, w.hflag.p,
                          (const int *)(phase == 2 && poll ? w.ready.p : nullptr), spin_limit);
-    } else {
-      allow_lds(k_vit_wide_fix<false>, ldsf);
-      hipLaunchKernelGGL((k_vit_wide_fix<false>), dim3(b->n), dim3(256), ldsf, s2, iv, em, vc, m->N, m->NP, (const double *)m->lt.p,
-                         (const double *)m->pi.p, (const double *)nullptr, b->TBW, b->tb.p, b->last_state.p, b->vit_lp.p,
-                         sw.stats.p, (const double *)w.rows2.p, (const double *)w.BL.p, w.sel_from.p, w.sel_hyp.p,
-                         (const double *)w.pre.p, phase, (const int64_t *)w.hstop.p, w.hvec.p, w.hflag.p,
-                         (const int *)(phase == 2 && poll ? w.ready.p : nullptr), spin_limit);
-    }
+    });
   };
   if (head) {
     (void)hipEventRecord(b->evX[0], st);
@@ -2494,19 +2491,13 @@ static int viterbi_wide_cp(tehmm_batch *b, const tehmm_model *m, const IntervalT
     HIPCHK(w.wk_e.ensure(w.h_wke.size() + 8));
     HIPCHK(hipMemcpyAsync(w.wk_c.p, w.h_wkc.data(), w.h_wkc.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(w.wk_e.p, w.h_wke.data(), w.h_wke.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    if (ratio) {
-      allow_lds(k_vit_wide_spec<true, true>, lds);
-      hipLaunchKernelGGL((k_vit_wide_spec<true, true>), dim3(nwg2), dim3(512), lds, st, iv, vc, m->N, m->NP,
-                         (const double *)m->lt.p, (const double *)w.BL.p, (const double *)b->ratios.p,
-                         (const int *)w.wk_c.p, (const int *)w.wk_e.p, b->TBW, w.tb1.p, w.tb2.p, w.rows2.p, wide_vit_warmup(CS), w.pre.p,
-                         w.ready.p);
-    } else {
-      allow_lds(k_vit_wide_spec<true, false>, lds);
-      hipLaunchKernelGGL((k_vit_wide_spec<true, false>), dim3(nwg2), dim3(512), lds, st, iv, vc, m->N, m->NP,
-                         (const double *)m->lt.p, (const double *)w.BL.p, (const double *)nullptr,
-                         (const int *)w.wk_c.p, (const int *)w.wk_e.p, b->TBW, w.tb1.p, w.tb2.p, w.rows2.p, wide_vit_warmup(CS), w.pre.p,
-                         w.ready.p);
-    }
+    bool_dispatch(ratio, [&](auto r) {
+      allow_lds(k_vit_wide_spec<r>, lds);
+      hipLaunchKernelGGL((k_vit_wide_spec<r>), dim3(nwg2), dim3(512), lds, st, iv, vc, m->N, m->NP,
+                         (const double *)m->lt.p, (const double *)w.BL.p, (const double *)(r ? b->ratios.p : nullptr),
+                         (const int *)w.wk_c.p, (const int *)w.wk_e.p, b->TBW, w.tb1.p, w.tb2.p, w.rows2.p,
+                         std::min(CS, kn.wide_vit_warmup), w.pre.p, w.ready.p);
+    });
   }
   (void)hipEventRecord(ev_spec, st);                 // the throughput passes are behind: what follows is latency-bound
   // the exact chain
@@ -3011,12 +3002,12 @@ static int eval_posterior(EvalCtx &c, int half) {
   } else {
     // 64 <= N <= 128: the chunk-parallel passes are enqueued; their verdict is read behind the Viterbi enqueue
     // (eval_finish_wide), so the two pipelines share the GPU
-    rc = posterior_wide_cp(b, m, iv, c.em, st, b->ev[eP + 1], &c.wide_pending,
+    rc = posterior_wide_cp(b, m, iv, c.em, c.kn, st, b->ev[eP + 1], &c.wide_pending,
                            c.wide_vit ? (const double *)b->ww.BL.p : nullptr);
     if (rc) return rc;
     if (!c.wide_pending) {
-      if (p.SPL == 1) launch_posterior<1>(b, m, iv, c.em, st, b->ev[eP + 1]);
-      else launch_posterior<2>(b, m, iv, c.em, st, b->ev[eP + 1]);
+      if (p.SPL == 1) launch_posterior<1>(b, m, iv, c.em, c.kn.wide, st, b->ev[eP + 1]);
+      else launch_posterior<2>(b, m, iv, c.em, c.kn.wide, st, b->ev[eP + 1]);
     }
   }
   (void)hipEventRecord(b->ev[eP + 2], st);
@@ -3029,12 +3020,12 @@ static int eval_finish_wide(EvalCtx &c) {
   tehmm_batch *b = c.b;
   hipStream_t st = b->sP;
   bool wide_done = false;
-  int rc = posterior_wide_finish(b, c.m, c.iv, st, b->ev[eP + 1], &wide_done);
+  int rc = posterior_wide_finish(b, c.m, c.iv, c.kn, st, b->ev[eP + 1], &wide_done);
   if (rc) return rc;
   c.wide_cp = wide_done;
   if (!wide_done) {
-    if (c.p.SPL == 1) launch_posterior<1>(b, c.m, c.iv, c.em, st, b->ev[eP + 1]);
-    else launch_posterior<2>(b, c.m, c.iv, c.em, st, b->ev[eP + 1]);
+    if (c.p.SPL == 1) launch_posterior<1>(b, c.m, c.iv, c.em, c.kn.wide, st, b->ev[eP + 1]);
+    else launch_posterior<2>(b, c.m, c.iv, c.em, c.kn.wide, st, b->ev[eP + 1]);
   }
   (void)hipEventRecord(b->ev[eP + 2], st);
   return TEHMM_OK;
@@ -3232,11 +3223,11 @@ static int eval_viterbi(EvalCtx &c) {
   } else if (p.coop) {
     nt_dispatch(m->NP, [&](auto nt) { launch_vit_coop<nt>(b, m, iv, c.em, p.ratio, st); });
   } else {
-    rc = viterbi_wide_cp(b, m, iv, c.em, p.ratio, st, b->ev[eV + 3], &c.wide_vit);
+    rc = viterbi_wide_cp(b, m, iv, c.em, p.ratio, c.kn, st, b->ev[eV + 3], &c.wide_vit);
     if (rc) return rc;
     if (!c.wide_vit) {
-      if (p.SPL == 1) launch_viterbi<1>(b, m, iv, c.em, p.ratio, st);
-      else launch_viterbi<2>(b, m, iv, c.em, p.ratio, st);
+      if (p.SPL == 1) launch_viterbi<1>(b, m, iv, c.em, p.ratio, c.kn.wide, st);
+      else launch_viterbi<2>(b, m, iv, c.em, p.ratio, c.kn.wide, st);
     }
     if (p.wide_defer) {
       // the posterior passes go behind the quantised Viterbi pass, next to the exact chain (few CUs, latency-bound)
@@ -4124,16 +4115,9 @@ void launch_estep(const tehmm_model *m, const IntervalTab &iv, const EmisTab &em
 // 16-item tile and step (~9 ns per row and CU), a track in LDS ~190-270 ns (nine ds_add_f64 at ~1 lane per cycle,
 // more when items share a symbol), and the LDS kernel's workgroups do not share a CU with the 416-register waves
 // of the one-hot kernel, so the two add up rather than overlap: break-even near 40 rows.
-// TEHMM_ESTEP_SMALL overrides (largest track, in rows, that takes the one-hot product).
-#define TEHMM_ESTEP_SMALL_DEFAULT 40
-static int estep_small_threshold(const tehmm_model *) {
-  if (const char *sm = std::getenv("TEHMM_ESTEP_SMALL")) return std::atoi(sm);
-  return TEHMM_ESTEP_SMALL_DEFAULT;
-}
-
-static void estep_build_groups(const tehmm_model *m, int cap_rows, EstepGroups &eg) {
+// TEHMM_ESTEP_SMALL overrides (largest track, in rows, that takes the one-hot product): EvalKnobs::estep_small.
+static void estep_build_groups(const tehmm_model *m, int cap_rows, int small, EstepGroups &eg) {
   std::memset(&eg, 0, sizeof(eg));
-  const int small = estep_small_threshold(m);
   std::vector<int> big;
   int row = 0;
   for (int i = 0; i < TEHMM_ESTEP_MAXRT * 16; ++i) eg.rt_info[i] = -1;
@@ -4174,9 +4158,9 @@ static void estep_build_groups(const tehmm_model *m, int cap_rows, EstepGroups &
   eg.first[bins.size()] = slot;
 }
 
-static bool estep_fused_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio, int CS) {
-  const char *s = std::getenv("TEHMM_ESTEP_FUSED");
-  if (s && std::atoi(s) == 0) return false;
+static bool estep_fused_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio, const EvalKnobs &kn) {
+  const int CS = kn.spec_chunk;
+  if (!kn.estep_fused) return false;
   if (ratio || m->N >= 64 || m->NP > 64 || CS <= 0 || b->total < 2 * (int64_t)CS) return false;
   if (!m->ptab.p || m->K > 78 || m->K > 127) return false;
   for (int k = 0; k < m->K; ++k)
@@ -4242,12 +4226,12 @@ static int launch_estep_reduce(tehmm_batch *b, const tehmm_model *m, const Inter
 }
 
 // returns TEHMM_OK and *done = true when the fused path ran; *done = false: the caller falls back
-static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, double *lp_out, int *dead_out, bool *done) {
+static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, const EvalKnobs &kn, double *dev_stats, double *lp_out, int *dead_out,
+                       bool *done) {
   *done = false;
-  const EvalKnobs kn = read_eval_knobs();
   b->lw.rix_ref = kn.rowindex_ref;
   const int CS = kn.spec_chunk;
-  if (!estep_fused_wanted(m, b, false, CS)) return TEHMM_OK;
+  if (!estep_fused_wanted(m, b, false, kn)) return TEHMM_OK;
   const int LS = lane_sub_size(CS, b->total, kn.lane_sub);
   if (LS <= 0) return TEHMM_OK;
   LaneWork &lw = b->lw;
@@ -4277,7 +4261,7 @@ static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, do
   }
   if (w.groups_model != m->uid || !w.d_groups.p) {
     const int cap_rows = (int)((160 * 1024 - (size_t)m->K * sizeof(int) - 64) / ((size_t)m->NP * sizeof(double)));
-    estep_build_groups(m, cap_rows, w.h_groups);
+    estep_build_groups(m, cap_rows, kn.estep_small, w.h_groups);
     HIPCHK(w.d_groups.upload(&w.h_groups, 1));
     w.groups_model = m->uid;
   }
@@ -4348,16 +4332,8 @@ static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, double *dev_stats, do
 
 // ---- E-step on the item-parallel passes of tehmm_wide.hip.h (tehmm_wide_estep.hip.h): 64 <= N <= 128 states, and
 // segment ratios at any N <= 128 ---------------------------------------------------------------------------------
-static int wide_estep_npw(int N) {
-  static const int sizes[] = {16, 32, 48, 64, 80, 96, 112, 128};
-  for (int sz : sizes)
-    if (N <= sz) return sz;
-  return 0;
-}
-
-static bool estep_wide_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio) {
-  int mode = 1;                                     // 0: off, 1: where the fused passes do not apply, 2: everywhere
-  if (const char *s = std::getenv("TEHMM_ESTEP_WIDE")) mode = std::atoi(s);
+static bool estep_wide_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio, const EvalKnobs &kn) {
+  const int mode = kn.estep_wide;                   // 0: off, 1: where the fused passes do not apply, 2: everywhere
   if (mode == 0 || m->N > 128 || b->total < 1024) return false;
   if (mode == 1 && !(ratio || m->N >= 64)) return false;
   if (m->K > 255) return false;
@@ -4366,7 +4342,7 @@ static bool estep_wide_wanted(const tehmm_model *m, const tehmm_batch *b, bool r
 
 template <int NPW>
 static int launch_wide_estep_reduce(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const LaneGeom &lg, bool ratio,
-                                    double *dev_stats, hipStream_t st) {
+                                    const EvalKnobs &kn, double *dev_stats, hipStream_t st) {
   WideWork &w = b->ww;
   using G = WideEstepGeom<NPW>;
   const int64_t n_tiles = ((int64_t)w.n_items + 15) / 16;
@@ -4376,10 +4352,7 @@ static int launch_wide_estep_reduce(tehmm_batch *b, const tehmm_model *m, const 
   // 1024 SIMDs), ranges of 16 positions or more
   int SQ = 1;
   while (SQ < 8 && n_tiles * SQ < 4096 && w.L / (2 * SQ) >= 16 && w.L % (2 * SQ) == 0) SQ *= 2;
-  if (const char *sq = std::getenv("TEHMM_WIDE_ESTEP_SQ")) {
-    const int v = std::atoi(sq);
-    if (v >= 1 && w.L % v == 0) SQ = v;
-  }
+  if (kn.wide_estep_sq >= 1 && w.L % kn.wide_estep_sq == 0) SQ = kn.wide_estep_sq;
   const int64_t n_units = n_tiles * SQ;
   // xi: two workgroups per CU at most; gamma product: one unit per workgroup at a time, partial buffer <= 128 MB
   const int gxm = (int)std::max<int64_t>(1, std::min<int64_t>((n_units + G::TPW - 1) / G::TPW, 512));
@@ -4392,7 +4365,7 @@ static int launch_wide_estep_reduce(tehmm_batch *b, const tehmm_model *m, const 
   HIPCHK(w.part_rows.ensure((size_t)gxr * 4 * nrt * 16 * NPW));
   // the products are independent: the gamma product and the LDS histograms run on their own streams next to the xi
   // product (TEHMM_WIDE_ESTEP_SERIAL=1: one after the other, for profiling)
-  const bool serial = std::getenv("TEHMM_WIDE_ESTEP_SERIAL") != nullptr;
+  const bool serial = kn.wide_estep_serial;
   hipStream_t sB = serial ? st : b->sB, sV = serial ? st : b->sV;
   (void)hipEventRecord(b->evX[0], st);
   (void)hipStreamWaitEvent(sB, b->evX[0], 0);
@@ -4453,16 +4426,15 @@ static int launch_wide_estep_reduce(tehmm_batch *b, const tehmm_model *m, const 
 }
 
 // returns TEHMM_OK and *done = true when the path ran; *done = false: the caller falls back
-static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *dev_stats, double *lp_out, int *dead_out, bool *done) {
+static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, const EvalKnobs &kn, bool ratio, double *dev_stats, double *lp_out,
+                      int *dead_out, bool *done) {
   *done = false;
-  if (!estep_wide_wanted(m, b, ratio)) return TEHMM_OK;
-  const int NPW = wide_estep_npw(m->N);
+  if (!estep_wide_wanted(m, b, ratio, kn)) return TEHMM_OK;
+  const int NPW = wide_npw<TEHMM_WIDE_ESTEP_WIDTHS>(m->N);
   if (NPW <= 0) return TEHMM_OK;
   WideWork &w = b->ww;
   if (!w.h_flags) HIPCHK(hipHostMalloc((void **)&w.h_flags, 64, hipHostMallocDefault));
-  // item length: as posterior_wide_cp (enough items to give every SIMD a tile, 64 <= L <= 512, multiple of 32)
-  int L = (int)std::min<int64_t>(512, std::max<int64_t>(64, (b->total / (16 * 1024) + 31) & ~31));
-  if (const char *ls = std::getenv("TEHMM_WIDE_SUB")) L = std::max(32, (std::atoi(ls) + 31) & ~31);
+  const int L = wide_item_length(b, kn);
   if (!(w.GAM.p && w.L == L && w.NPW == NPW)) {
     // emission rows + three float rows per position must fit
     size_t free_b = 0, total_b = 0;
@@ -4498,7 +4470,7 @@ static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *de
     WideLds &wl = w.h_lds;
     std::memset(&wl, 0, sizeof(wl));
     for (int i = 0; i < TEHMM_ESTEP_MAXRT * 16; ++i) { wr.info[i] = -1; wr.grow[i] = 0; }
-    const int small = estep_small_threshold(m);
+    const int small = kn.estep_small;
     constexpr size_t kLdsCap = 150 * 1024;
     int big_rows = 0;
     for (int k = 0; k < m->K; ++k)
@@ -4545,9 +4517,7 @@ static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *de
   IntervalTab iv;
   EmisTab em;
   fill_tabs(m, b, iv, em, ratio);     // fit applies the ratios to emissions too (basehmm.py:510)
-  LaneGeom lg;
-  lg.item_iv = w.item_iv.p; lg.item_t0 = w.item_t0.p; lg.ifirst = w.ifirst.p;
-  lg.n_items = w.n_items; lg.n_groups = w.n_groups; lg.L = L;
+  const LaneGeom lg = wide_lane_geom(w);
   hipStream_t st = b->sP;
   b->tnames.clear();
   b->tpairs.clear();
@@ -4557,42 +4527,13 @@ static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *de
   launch_wide_emis(b, m, iv, em, lg, ratio ? 3 : 2, nullptr, st);
   (void)hipEventRecord(b->ev[12], st);
   (void)hipEventRecord(b->ev[9], st);
-  // warm-up: what the last E-step with this model handle needed (the parameters move a little per iteration; the links
-  // are verified whatever the guess), 64 positions to begin with
-  constexpr int kWuMax = 1024;
-  int Wu = 64;
-  if (const char *wus = std::getenv("TEHMM_LANE_WARMUP")) Wu = std::min(kWuMax, std::max(1, std::atoi(wus)));
-  else if (w.wu_ok > 0 && w.wu_model == m->uid) Wu = w.wu_ok;
-  int attempts = 0;
-  for (;;) {
-    if (int rc = wide_post_attempt(b, m, iv, Wu, st, b->ev[8], true)) return rc;
-    w.pp_active = false;
-    ++attempts;
-    HIPCHK(hipStreamSynchronize(st));
-    if (w.h_flags[0] > 0) return TEHMM_OK;             // impossible rows: the sequential kernels own their semantics
-    if (w.h_flags[1] == 0) break;
-    if (Wu >= kWuMax) return TEHMM_OK;                 // does not forget: the caller falls back
-    Wu = std::min(kWuMax, 2 * Wu);
-    HIPCHK(hipMemsetAsync(w.flags.p, 0, 4 * sizeof(int), st));
-    (void)hipEventRecord(b->ev[9], st);
-  }
-  w.wu_ok = Wu;
-  w.wu_model = m->uid;
-  w.wu_version = m->version;
-  (void)hipEventRecord(b->ev[6], st);
-  hipLaunchKernelGGL(k_wide_loglik, dim3((b->n + 3) / 4), dim3(256), 0, st, iv, lg, m->N, NPW, (const double *)w.end_f.p,
-                     (const double *)w.SL.p, (const double *)w.lr.p, b->fwd_lp.p);
+  if (int rc = wide_post_attempt(b, m, iv, kn, wide_first_warmup(w, m, kn, false), st, b->ev[8], true)) return rc;
+  WideRetries re = {b->ev[9], b->ev[6], 1};
+  bool verified = false;
+  if (int rc = wide_verdict(b, m, iv, kn, st, b->ev[8], true, &re, &verified)) return rc;
+  if (!verified) return TEHMM_OK;                      // the caller falls back
   int rcr = TEHMM_OK;
-  switch (NPW) {
-    case 16: rcr = launch_wide_estep_reduce<16>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 32: rcr = launch_wide_estep_reduce<32>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 48: rcr = launch_wide_estep_reduce<48>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 64: rcr = launch_wide_estep_reduce<64>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 80: rcr = launch_wide_estep_reduce<80>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 96: rcr = launch_wide_estep_reduce<96>(b, m, iv, lg, ratio, dev_stats, st); break;
-    case 112: rcr = launch_wide_estep_reduce<112>(b, m, iv, lg, ratio, dev_stats, st); break;
-    default: rcr = launch_wide_estep_reduce<128>(b, m, iv, lg, ratio, dev_stats, st); break;
-  }
+  nt_dispatch_of<TEHMM_WIDE_ESTEP_WIDTHS>(NPW, [&](auto npw) { rcr = launch_wide_estep_reduce<npw>(b, m, iv, lg, ratio, kn, dev_stats, st); });
   if (rcr) return rcr;
   (void)hipEventRecord(b->ev[7], st);
   HIPCHK(hipGetLastError());
@@ -4607,9 +4548,9 @@ static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *de
     b->tms.push_back((double)ms);
   }
   b->tnames.push_back("count:wide_estep_attempts");
-  b->tms.push_back((double)attempts);
+  b->tms.push_back((double)re.attempts);
   b->tnames.push_back("count:wide_estep_warmup");
-  b->tms.push_back((double)Wu);
+  b->tms.push_back((double)w.wu_ok);
   std::vector<double> lp((size_t)b->n);
   HIPCHK(hipMemcpy(lp.data(), b->fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
   double lp_total = 0.0;
@@ -4641,14 +4582,14 @@ static int estep_accumulate(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, 
   const int N = m->N, NP = m->NP;
   {
     bool done = false;
-    const char *wm = std::getenv("TEHMM_ESTEP_WIDE");
-    const bool wide_first = wm && std::atoi(wm) == 2;
+    const EvalKnobs kn = read_eval_knobs();
+    const bool wide_first = kn.estep_wide == 2;
     if (!ratio && N < 64 && !wide_first) {
-      int rcf = estep_fused(m, b, dev_stats, lp_out, dead_out, &done);
+      int rcf = estep_fused(m, b, kn, dev_stats, lp_out, dead_out, &done);
       if (rcf) return rcf;
       if (done) return TEHMM_OK;
     }
-    int rcw = estep_wide(m, b, ratio, dev_stats, lp_out, dead_out, &done);
+    int rcw = estep_wide(m, b, kn, ratio, dev_stats, lp_out, dead_out, &done);
     if (rcw) return rcw;
     if (done) return TEHMM_OK;
     if (N >= 64)

@@ -567,8 +567,8 @@ __global__ __launch_bounds__(256) void k_wide_logrows(IntervalTab iv, EmisTab em
   }
 }
 
-// block = 512: eight chunks of one binade (wk_c [8 per workgroup], -1 = none; wk_e [workgroup]); QUANT = false:
-// plain fp64 gains of every listed chunk (P0).  LDS: table [N][128] | flag
+// block = 512: eight chunks of one binade (wk_c [8 per workgroup], -1 = none; wk_e [workgroup]).  The plain gains that
+// place the chunks in their binades (P0) come from k_vit_wide_gain.  LDS: table [N][128] | flag
 //
 // Rounding ties.  Where an addend of the reference's sum (b, lt[j][j] r, lt[j][j] (r - 1)) lies exactly between two
 // grid points, fl(v + z) depends on the PARITY of v / u -- candidate by candidate, because the reference adds b and
@@ -581,7 +581,7 @@ __global__ __launch_bounds__(256) void k_wide_logrows(IntervalTab iv, EmisTab em
 // its own parity, and the recurrence stays exact THROUGH the tie.  Two vectors, two sets of recorded rows and of
 // traceback bytes (the second set written from the chunk's first tie on: before it the hypotheses agree); the chain
 // learns delta when it verifies the chunk and adopts the set whose parity matches.
-template <bool QUANT, bool RATIO>
+template <bool RATIO>
 __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks vc, int N, int NP,
                                                        const double *__restrict__ g_lt, const double *__restrict__ BL,
                                                        const double *__restrict__ tratios, const int *__restrict__ wk_c,
@@ -590,25 +590,25 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
   extern __shared__ double wsm[];
   double *tq = wsm;
   volatile int *tflag = (volatile int *)(wsm + (size_t)N * TEHMM_WIDE_S);
-  const int e = QUANT ? wk_e[blockIdx.x] : 0;
-  const double u = QUANT ? ldexp(1.0, e - 52) : 0.0;
-  const double M = QUANT ? ldexp(1.5, e) : 0.0;                 // fl(z + M) - M rounds z to the grid u
+  const int e = wk_e[blockIdx.x];
+  const double u = ldexp(1.0, e - 52);
+  const double M = ldexp(1.5, e);                               // fl(z + M) - M rounds z to the grid u
   const double half_u = 0.5 * u;
-  const double CM = QUANT ? ldexp(1.0, e + 1) - ldexp(1.0, e - 44) : 0.0;          // 2^(e+1) - 256 u
-  const double wlim = QUANT ? -(ldexp(1.0, e) - ldexp(1.5, e - 44)) : -INFINITY;   // -(2^e - 384 u)
-  const double zlim = QUANT ? ldexp(1.0, e - 1) : INFINITY;
-  const double i2u = QUANT ? ldexp(1.0, 51 - e) : 0.0;                             // 1 / (2 u)
+  const double CM = ldexp(1.0, e + 1) - ldexp(1.0, e - 44);          // 2^(e+1) - 256 u
+  const double wlim = -(ldexp(1.0, e) - ldexp(1.5, e - 44));         // -(2^e - 384 u)
+  const double zlim = ldexp(1.0, e - 1);
+  const double i2u = ldexp(1.0, 51 - e);                             // 1 / (2 u)
   // LDS behind the table: flag | number of tie entries | tie entries (from | to << 8 | parity of the lower neighbour << 16)
   volatile int *ntt = tflag + 1;
   volatile int *ttab = tflag + 2;
   int *hbig = (int *)(tflag + 2 + TEHMM_WIDE_MAXTT);             // [4]: states with a "never" transition into them
   if (threadIdx.x == 0) { *tflag = 0; *ntt = 0; hbig[0] = hbig[1] = hbig[2] = hbig[3] = 0; }
   __syncthreads();
-  const double zhuge = QUANT ? -ldexp(1.0, e + 1) : -INFINITY;
+  const double zhuge = -ldexp(1.0, e + 1);
   for (int i = threadIdx.x; i < N * TEHMM_WIDE_S; i += blockDim.x) {
     const int f = i >> 7, j = i & 127;
     double z = j < N ? g_lt[(size_t)f * NP + j] : -INFINITY;
-    if (QUANT && z > -INFINITY && z <= zhuge) {
+    if (z > -INFINITY && z <= zhuge) {
       // a "never" transition (the reference's log(0) = -1e100): V[f] + z lies below everything a candidate with an
       // ordinary transition reaches from inside the binade (V <= -2^e, z <= -2^(e+1), ordinary |z'| < 2^(e-1)), so it
       // counts as -inf here -- as long as the state has such a candidate from a live state: a state that comes out
@@ -616,37 +616,33 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
       atomicOr(&hbig[j >> 5], 1 << (j & 31));
       z = -INFINITY;
     }
-    double val = z;
-    if (QUANT) {
-      double q = (z + M) - M;
-      if (z > -INFINITY && !(fabs(z) < zlim)) *tflag = 1;       // out of the range of the rounding trick
-      if (z > -INFINITY && fabs(z - q) == half_u) {
-        // a transition exactly between two grid points: fl(V[f] + z) depends on the parity of V[f] / u.  The table
-        // holds the LOWER neighbour; the step adds u where round-half-even goes up (k_vit_wide_spec, tie_adj)
-        const double qo = 2.0 * z - q;                          // the odd neighbour (q / u is even)
-        const int k = atomicAdd((int *)ntt, 1);
-        if (k < TEHMM_WIDE_MAXTT) ttab[k] = f | (j << 8) | ((qo < q ? 1 : 0) << 16);
-        else *tflag = 1;
-        q = fmin(q, qo);
-      }
-      val = 128.0 * q + (double)(127 - f) * u;                  // -inf stays -inf
+    double q = (z + M) - M;
+    if (z > -INFINITY && !(fabs(z) < zlim)) *tflag = 1;         // out of the range of the rounding trick
+    if (z > -INFINITY && fabs(z - q) == half_u) {
+      // a transition exactly between two grid points: fl(V[f] + z) depends on the parity of V[f] / u.  The table
+      // holds the LOWER neighbour; the step adds u where round-half-even goes up (k_vit_wide_spec, tie_adj)
+      const double qo = 2.0 * z - q;                            // the odd neighbour (q / u is even)
+      const int k = atomicAdd((int *)ntt, 1);
+      if (k < TEHMM_WIDE_MAXTT) ttab[k] = f | (j << 8) | ((qo < q ? 1 : 0) << 16);
+      else *tflag = 1;
+      q = fmin(q, qo);
     }
-    tq[i] = val;
+    tq[i] = 128.0 * q + (double)(127 - f) * u;                  // -inf stays -inf
   }
   __syncthreads();
-  const int n_tt = QUANT ? min((int)*ntt, TEHMM_WIDE_MAXTT) : 0;
+  const int n_tt = min((int)*ntt, TEHMM_WIDE_MAXTT);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = wk_c[blockIdx.x * 8 + w];
   if (c < 0) return;
   const int id = vc.iv[c];
   const int64_t p0 = iv.pos0[id], t0 = vc.t0[c];
   const int CS = vc.CS;
-  const int len = (int)min((int64_t)CS, iv.len[id] - t0);     // (P0 also runs ragged tails; P2 only full chunks)
+  const int len = (int)min((int64_t)CS, iv.len[id] - t0);     // (only full chunks are speculated)
   const bool live0 = lane < N, live1 = lane + 64 < N;
-  const bool big0 = QUANT && ((hbig[lane >> 5] >> (lane & 31)) & 1) != 0;
-  const bool big1 = QUANT && ((hbig[2 + (lane >> 5)] >> (lane & 31)) & 1) != 0;
-  constexpr int H = QUANT ? 2 : 1;
-  double W0[H], W1[H], base[H];          // QUANT: 128 x (value - base) of the lane's two states, per hypothesis
+  const bool big0 = ((hbig[lane >> 5] >> (lane & 31)) & 1) != 0;
+  const bool big1 = ((hbig[2 + (lane >> 5)] >> (lane & 31)) & 1) != 0;
+  constexpr int H = 2;
+  double W0[H], W1[H], base[H];          // 128 x (value - base) of the lane's two states, per hypothesis
   int pb[H];                             // parity of base / u, XOR the hypothesis
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -659,16 +655,16 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
   // transition table itself has tie entries: their rounding follows the hypothesis at every step)
   int nt = 0, first_tie = n_tt > 0 ? 0 : CS;
   bool diverged = n_tt > 0;
-  bool bad = QUANT && *tflag != 0;
+  bool bad = *tflag != 0;
   const double ltd0 = live0 ? g_lt[(size_t)lane * NP + lane] : 0.0;
   const double ltd1 = live1 ? g_lt[(size_t)(lane + 64) * NP + lane + 64] : 0.0;
   const double lt00 = g_lt[0];
-  const double lt00q = QUANT ? (lt00 + M) - M : lt00;
-  if (QUANT && RATIO && (fabs(lt00 - lt00q) == half_u || !(fabs(lt00) < zlim))) bad = true;
-  // QUANT: the pass starts WU positions BEFORE its chunk (a speculated chunk is never an interval's first), so that
+  const double lt00q = (lt00 + M) - M;
+  if (RATIO && (fabs(lt00 - lt00q) == half_u || !(fabs(lt00) < zlim))) bad = true;
+  // The pass starts WU positions BEFORE its chunk (a speculated chunk is never an interval's first), so that
   // by the chunk's first position it has forgotten its zero start: `pre` [hypothesis][chunk][NP] keeps the vector
   // at position t0 - 1, against which the chain can verify the chunk without walking a single step of it
-  const int s_first = QUANT ? -WU : 0;
+  const int s_first = -WU;
   const double *bp = BL + (p0 + t0) * TEHMM_WIDE_S;
   double bn0 = bp[(int64_t)s_first * TEHMM_WIDE_S + lane], bn1 = bp[(int64_t)s_first * TEHMM_WIDE_S + lane + 64];
   const int n0 = min(N, 64);
@@ -680,7 +676,7 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
       bn1 = bp[(int64_t)(s + 1) * TEHMM_WIDE_S + lane + 64];
     }
     // ---- segment-ratio terms of this position
-    double add0 = 0.0, add1 = 0.0;       // what every candidate from >= 1 gets (QUANT: grid-rounded, not yet x 128)
+    double add0 = 0.0, add1 = 0.0;       // what every candidate from >= 1 gets (grid-rounded, not yet x 128)
     double dz0 = 0.0, dz1 = 0.0;         // what candidate 0 gets on top of that
     double za0 = 0.0, za1 = 0.0, zb0 = 0.0, zb1 = 0.0, qa0 = 0.0, qa1 = 0.0, qb0 = 0.0, qb1 = 0.0;
     bool tza0 = false, tza1 = false, tzb0 = false, tzb1 = false, rg = false;
@@ -689,27 +685,21 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
       rg = r > 1.0;
       za0 = ltd0 * r; za1 = ltd1 * r;                          // from == 0: lt[j][j] * r, always
       zb0 = ltd0 * (r - 1.0); zb1 = ltd1 * (r - 1.0);          // from >= 1: lt[j][j] * (r - 1) if r > 1
-      if (QUANT) {
-        qa0 = (za0 + M) - M; qa1 = (za1 + M) - M;
-        qb0 = rg ? (zb0 + M) - M : 0.0; qb1 = rg ? (zb1 + M) - M : 0.0;
-        tza0 = live0 && fabs(za0 - qa0) == half_u;
-        tza1 = live1 && fabs(za1 - qa1) == half_u;
-        tzb0 = live0 && rg && fabs(zb0 - qb0) == half_u;
-        tzb1 = live1 && rg && fabs(zb1 - qb1) == half_u;
-        bad = bad || (live0 && !(fabs(za0) < zlim)) || (live1 && !(fabs(za1) < zlim));
-        add0 = qb0; add1 = qb1;
-        dz0 = (qa0 - qb0) - (lane == 0 ? lt00q : 0.0);
-        dz1 = qa1 - qb1;
-      } else {
-        add0 = rg ? zb0 : 0.0; add1 = rg ? zb1 : 0.0;
-        dz0 = (za0 - add0) - (lane == 0 ? lt00 : 0.0);
-        dz1 = za1 - add1;
-      }
+      qa0 = (za0 + M) - M; qa1 = (za1 + M) - M;
+      qb0 = rg ? (zb0 + M) - M : 0.0; qb1 = rg ? (zb1 + M) - M : 0.0;
+      tza0 = live0 && fabs(za0 - qa0) == half_u;
+      tza1 = live1 && fabs(za1 - qa1) == half_u;
+      tzb0 = live0 && rg && fabs(zb0 - qb0) == half_u;
+      tzb1 = live1 && rg && fabs(zb1 - qb1) == half_u;
+      bad = bad || (live0 && !(fabs(za0) < zlim)) || (live1 && !(fabs(za1) < zlim));
+      add0 = qb0; add1 = qb1;
+      dz0 = (qa0 - qb0) - (lane == 0 ? lt00q : 0.0);
+      dz1 = qa1 - qb1;
     }
-    const double bq0 = QUANT ? (b0 + M) - M : 0.0, bq1 = QUANT ? (b1 + M) - M : 0.0;
-    const bool tb0 = QUANT && live0 && fabs(b0 - bq0) == half_u, tb1 = QUANT && live1 && fabs(b1 - bq1) == half_u;
-    const bool anytie = QUANT && __any(tb0 || tb1 || tza0 || tza1 || tzb0 || tzb1);
-    if (QUANT) bad = bad | (b0 != b0);
+    const double bq0 = (b0 + M) - M, bq1 = (b1 + M) - M;
+    const bool tb0 = live0 && fabs(b0 - bq0) == half_u, tb1 = live1 && fabs(b1 - bq1) == half_u;
+    const bool anytie = __any(tb0 || tb1 || tza0 || tza1 || tzb0 || tzb1);
+    bad = bad | (b0 != b0);
     // ---- transitions that are rounding ties in this binade (rare: a handful per binade at most): the table holds
     // the lower neighbour of fl(V[f] + lt); round-half-even takes the upper one when the lower one is odd, i.e. when
     // parity(V[f] / u) differs from the parity of the entry's lower neighbour.  +128 u for that (from, to), else 0.
@@ -732,8 +722,8 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
       const double s0 = wide_readlane(W0[h], 0);
       double x0 = s0 + tq[lane], x1 = s0 + tq[lane + 64];
       if (RATIO) {
-        x0 += QUANT ? 128.0 * dz0 : dz0;
-        x1 += QUANT ? 128.0 * dz1 : dz1;
+        x0 += 128.0 * dz0;
+        x1 += 128.0 * dz1;
       }
       // eight from-states at a time: their sixteen table entries are requested before the first is used (left as
       // a rolled loop every iteration waits for its own two LDS reads: 11 us per step)
@@ -766,25 +756,20 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
         x0 = fmax(x0, sv + tq[f * TEHMM_WIDE_S + lane]);
         x1 = fmax(x1, sv + tq[f * TEHMM_WIDE_S + lane + 64]);
       }
-      if (QUANT) {
-        for (int k = 0; k < n_tt; ++k) {      // (the loop above already holds these candidates at the lower neighbour)
-          double a0, a1;
-          const int f = tie_adj(hc, k, a0, a1);
-          const double sv = f < 64 ? wide_readlane(W0[h], f) : wide_readlane(W1[h], f - 64);
-          double c0 = sv + tq[f * TEHMM_WIDE_S + lane] + a0, c1 = sv + tq[f * TEHMM_WIDE_S + lane + 64] + a1;
-          if (RATIO && f == 0) {
-            c0 += 128.0 * dz0;
-            c1 += 128.0 * dz1;
-          }
-          x0 = fmax(x0, c0);
-          x1 = fmax(x1, c1);
+      for (int k = 0; k < n_tt; ++k) {        // (the loop above already holds these candidates at the lower neighbour)
+        double a0, a1;
+        const int f = tie_adj(hc, k, a0, a1);
+        const double sv = f < 64 ? wide_readlane(W0[h], f) : wide_readlane(W1[h], f - 64);
+        double c0 = sv + tq[f * TEHMM_WIDE_S + lane] + a0, c1 = sv + tq[f * TEHMM_WIDE_S + lane + 64] + a1;
+        if (RATIO && f == 0) {
+          c0 += 128.0 * dz0;
+          c1 += 128.0 * dz1;
         }
-        W0[h] = x0 + 128.0 * (bq0 + add0);    // (multiples of 128 u: the index bits ride along)
-        W1[h] = x1 + 128.0 * (bq1 + add1);
-      } else {
-        W0[h] = (x0 + b0) + add0;
-        W1[h] = (x1 + b1) + add1;
+        x0 = fmax(x0, c0);
+        x1 = fmax(x1, c1);
       }
+      W0[h] = x0 + 128.0 * (bq0 + add0);      // (multiples of 128 u: the index bits ride along)
+      W1[h] = x1 + 128.0 * (bq1 + add1);
     };
     // ---- both hypotheses, no tie at this position: one pass over the table for the two vectors (the pass is bound
     // by LDS bandwidth: 100 KB of table per step and wave)
@@ -913,10 +898,6 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
     };
     using H0 = std::integral_constant<int, 0>;
     using H1 = std::integral_constant<int, H - 1>;
-    if (!QUANT) {
-      fast(H0{});
-      continue;
-    }
     if (anytie) {
       first_tie = min(first_tie, max(s, 0));
       nt += s >= 0;
@@ -961,22 +942,17 @@ __global__ __launch_bounds__(512) void k_vit_wide_spec(IntervalTab iv, VitChunks
       }
     }
   }
-  if (QUANT) {
-    const unsigned long long anybad = __ballot(bad);
-    if (lane == 0) {
-      vc.ntie[c] = nt;
-      vc.ties[(int64_t)c * TEHMM_SPEC_MAXT] = first_tie;      // where the second set of traceback bytes starts
-      vc.ok[c] = anybad ? 0 : 1;
-    }
-    if (ready) {
-      // the exact chain may be waiting for this chunk (k_vit_wide_fix, `ready`): everything the wave wrote -- rows, pre,
-      // traceback bytes, ok -- is visible before the flag is
-      __threadfence();
-      if (lane == 0) __hip_atomic_store(&ready[c], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  } else {
-    const double g = wave_max_f64(fmax(live0 ? W0[0] : -INFINITY, live1 ? W1[0] : -INFINITY));
-    if (lane == 0) vc.gain[c] = g;
+  const unsigned long long anybad = __ballot(bad);
+  if (lane == 0) {
+    vc.ntie[c] = nt;
+    vc.ties[(int64_t)c * TEHMM_SPEC_MAXT] = first_tie;        // where the second set of traceback bytes starts
+    vc.ok[c] = anybad ? 0 : 1;
+  }
+  if (ready) {
+    // the exact chain may be waiting for this chunk (k_vit_wide_fix, `ready`): everything the wave wrote -- rows, pre,
+    // traceback bytes, ok -- is visible before the flag is
+    __threadfence();
+    if (lane == 0) __hip_atomic_store(&ready[c], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 

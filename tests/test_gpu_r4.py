@@ -362,6 +362,105 @@ def test_wide_estep_falls_back(monkeypatch):
         hm.close()
 
 
+def _wide_estep_twice(hm, model, obs, offs, r):
+    """Two E-steps of the same batch on the item-parallel passes: [(logprob, start, trans, obs statistics, interval
+    logprobs)] * 2 and the timing of the second."""
+    from tehmm_amd.engine import HipBatch
+    N = model.log_transmat.shape[0]
+    K, _, S = model.log_probs.shape
+    got, tm = [], None
+    for rep in range(2):
+        hb = HipBatch(obs, offs, r)
+        start, trans, st = np.zeros(N), np.zeros((N, N)), np.zeros((K, N, S))
+        lp = hm.estep(hb, r is not None, start, trans, st)
+        tm = hb.timing()
+        got.append((lp, start, trans, st, hb.interval_logprobs()))
+        hb.close()
+        assert "estep_emission_rows" in tm                                # the path under test ran
+    return got, tm
+
+
+def _check_wide_estep(got, model, obs, offs, r, tag):
+    """As test_wide_estep_vs_oracle: statistics at 1e-6 (observed error asserted at 3e-7), log-probability at 1e-9,
+    the second run bit-identical."""
+    from oracle import oracle
+    n = len(offs) - 1
+    ref = oracle.estep([obs[offs[i]:offs[i + 1]] for i in range(n)], model.log_probs, model.log_startprob,
+                       model.log_transmat, 1.0, [r[offs[i]:offs[i + 1]] for i in range(n)] if r is not None else None)
+    lp, start, trans, st, ilp = got[0]
+    assert_allclose(lp, ref["logprob"], rtol=1e-9)
+    assert_allclose(ilp.sum(), ref["logprob"], rtol=1e-9)
+    assert_allclose(start, ref["start"], rtol=1e-6, atol=1e-12)
+    assert_allclose(trans, ref["trans"], rtol=1e-6, atol=1e-9)
+    assert_allclose(st, ref["obs"], rtol=1e-6, atol=1e-9)
+    worst = max(_rel(start, ref["start"]), _rel(trans, ref["trans"], 1e-6), _rel(st, ref["obs"], 1e-6))
+    print("wide E-step %s: max rel error of the statistics %.3g" % (tag, worst))
+    assert worst <= 3e-7
+    for a, b in zip(got[0], got[1]):                                   # reproducible sums (ordered folds)
+        assert_array_equal(np.asarray(a), np.asarray(b))
+
+
+@pytest.mark.parametrize("N,use_ratios", [(70, False), (70, True), (90, False), (90, True)])
+def test_wide_estep_widths_80_and_96(monkeypatch, N, use_ratios):
+    """The E-step on the item-parallel passes at the two widths test_wide_estep_vs_oracle leaves out (70 states -> 80,
+    90 -> 96), with and without segment ratios, on 1 200 rows -- just above the path's 1 024-row floor, items of 64
+    positions: one-row, sub-item and multi-item intervals."""
+    from tehmm_amd import synth
+    from tehmm_amd.engine import HipModel
+    for k in KNOBS + ("TEHMM_ESTEP_WIDE", "TEHMM_WIDE_SUB", "TEHMM_LANE_WARMUP"):
+        monkeypatch.delenv(k, raising=False)
+    model = synth.make_model(N, (3, 5, 4), (), seed=12 + N)
+    offs = np.concatenate([[0], np.cumsum([700, 1, 70, 300, 129])]).astype(np.int64)
+    total = int(offs[-1])
+    obs = synth.sample_obs(model, total, seed=5, missing=0.02)
+    r = _seg_ratios(total, 7) if use_ratios else None
+    hm = HipModel(model.log_transmat, model.log_startprob, model.log_probs, 1.0, model.symbols_per_track)
+    got, _ = _wide_estep_twice(hm, model, obs, offs, r)
+    hm.close()
+    _check_wide_estep(got, model, obs, offs, r, "N=%d ratios=%s" % (N, use_ratios))
+
+
+def test_wide_warmup_retry_loop(monkeypatch):
+    """The verdict loop of the item-parallel passes really loops, for both of its users: a warm-up of one position
+    (TEHMM_LANE_WARMUP=1) cannot bring a link within 1e-8 for a model with memory, so the E-step and the posterior
+    evaluation must double it and attempt again -- and end at the same results as with the default first warm-up."""
+    from tehmm_amd import synth
+    from tehmm_amd.engine import HipBatch, HipModel
+    from oracle import oracle
+    for k in KNOBS + ("TEHMM_ESTEP_WIDE", "TEHMM_WIDE_SUB", "TEHMM_WIDE_CP", "TEHMM_WIDE_TOL", "TEHMM_LANE_WARMUP"):
+        monkeypatch.delenv(k, raising=False)
+    N = 70
+    model = synth.make_model(N, (3, 5, 4), (), seed=12 + N)
+    offs = np.concatenate([[0], np.cumsum([2500, 1800, 700])]).astype(np.int64)
+    obs = synth.sample_obs(model, int(offs[-1]), seed=5, missing=0.02)
+    hm = HipModel(model.log_transmat, model.log_startprob, model.log_probs, 1.0, model.symbols_per_track)
+
+    def posterior():
+        hb = HipBatch(obs, offs)
+        res = hm.eval(hb, viterbi=False, posterior=True)
+        out = (res["forward_logprob"].copy(), np.array(hb.posteriors()), hb.timing())
+        hb.close()
+        return out
+
+    flp0, post0, tm0 = posterior()
+    assert "count:wide_chunk_parallel_warmup" in tm0
+    monkeypatch.setenv("TEHMM_LANE_WARMUP", "1")
+    got, tm = _wide_estep_twice(hm, model, obs, offs, None)
+    print("wide E-step from warm-up 1: %d attempts, warm-up %d" % (tm["count:wide_estep_attempts"], tm["count:wide_estep_warmup"]))
+    assert tm["count:wide_estep_attempts"] >= 2 and tm["count:wide_estep_warmup"] >= 2
+    flp1, post1, tm1 = posterior()
+    print("wide posterior from warm-up 1: warm-up %d (default start: %d)"
+          % (tm1["count:wide_chunk_parallel_warmup"], tm0["count:wide_chunk_parallel_warmup"]))
+    assert tm1["count:wide_chunk_parallel_warmup"] >= 2
+    hm.close()
+    _check_wide_estep(got, model, obs, offs, None, "N=%d from warm-up 1" % N)
+    _, _, flp_o, post_o = oracle.eval_batch(obs, offs, model.log_probs, model.log_startprob, model.log_transmat,
+                                            1.0, None, n_threads=8)
+    assert_allclose(flp1, flp_o, rtol=1e-9)
+    assert_allclose(post1, post_o, rtol=1e-6, atol=1e-15)
+    assert_allclose(post1, post0, rtol=1e-6, atol=1e-15)
+
+
 def test_device_em_falls_back_to_the_host_loop_at_70_states(monkeypatch):
     """MultitrackHmm.fit at 70 states on a table with a row no state can emit: the item-parallel passes refuse it
     (TEHMM_ERR_UNSUPPORTED), _fit_device hands the whole fit to the reference's loop over the array-level entry points
