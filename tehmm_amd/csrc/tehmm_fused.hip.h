@@ -661,14 +661,73 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
   win.start((L + 2 * Wu - 1) / ft.SB);
   // Transposing store of the posterior rows.  A lane holds 9 scattered states of one item: stored directly,
   // every store instruction is 16 pieces of 32 bytes in 16 different rows, and the wave then spends ~40 % of its
-  // time waiting for them to retire.  Instead the 16 x N values of a step go through an LDS tile and leave as 9
-  // stores of 64 consecutive doubles of the [16][NT] tile: runs of up to 280 contiguous bytes per row.
+  // time waiting for them to retire.  Instead the 16 x N values of a step go through an LDS tile and leave in
+  // contiguous runs: as 16 stores of one row each (DEFER, below), or as 9 stores of 64 consecutive doubles of the
+  // [16][NT] tile, runs of up to 280 contiguous bytes per row (the log-domain form, in its tail).
+  // The stores leave ONE STEP LATE (round 6): the tail of step s only writes the tile; its row stores
+  // are issued between the MFMAs of the following iteration (post_slot below, beside es.slot(k)), where the matrix
+  // pipe covers the LDS round trip and the address arithmetic; behind the loop one flush stores the tile of step 0.
+  // One tile per wave is enough: an iteration reads all of it before its own tail rewrites it, and the LDS accesses
+  // of a wave execute in order.  Not in the log-domain form (LOGDOM, --emFac), whose loop carries more live values at
+  // every state count: at NT = 36 it spills 12 registers as it is and 18 with a row in flight, and the next form
+  // below (NT = 32) takes 252 of the 256 registers already.  One rule for the form, not a list of state counts: it keeps the
+  // element-wise store in its tail.
+  constexpr bool DEFER = !ESTEP && !LOGDOM;
   typedef __attribute__((address_space(3))) double lds_f64;
   typedef __attribute__((address_space(3))) long long lds_i64;
   const unsigned ptile = (unsigned)(size_t)(__attribute__((address_space(3))) const double *)fused_lds +
                          (unsigned)(ft.lds_rows * G::ROW_D_LDS * 8 + 4 * 2 * 3072 + (threadIdx.x >> 6) * (16 * NT * 8 + 128));
   const unsigned pinfo = ptile + 16 * NT * 8;
   if (!ESTEP && kq == 0) *(lds_i64 *)(size_t)(pinfo + (lane & 15) * 8) = run ? (long long)prow0 : -1ll;
+  // The deferred stores go ROW BY ROW: the 16 rows of the tile are 16 stores of N consecutive doubles, lane l writes
+  // column l mod N (lanes beyond N repeat the first columns: the same value to the same address).  A row's address is
+  // then a wave-uniform base (the item's row of step 0; scalar registers) plus one per-lane offset (s N + column) that all
+  // 16 stores of a step share: no per-element index arithmetic at all, where the element-wise form spent ~20 vector
+  // instructions per store.  Rows that do not exist (item not run, warm-up step, nothing yet) take the per-wave sink
+  // as their base, less s N, so that the same offset lands in it.
+  unsigned long long prow[16];
+  unsigned prun = 0;
+  unsigned long long psink = 0;
+  const int pcol = !DEFER ? 0 : lane < N ? lane : lane % N;
+  const unsigned pread = ptile + (unsigned)pcol * 8u;
+  if constexpr (DEFER) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long rb = *(lds_i64 *)(size_t)(pinfo + (unsigned)r * 8u);         // (the same address in every lane)
+      // (scalar registers at two waves per SIMD, where vector registers are what is short; the one-wave forms have
+      //  vector registers to spare and would spill scalar ones)
+      const unsigned rlo = (unsigned)rb, rhi = (unsigned)((unsigned long long)rb >> 32);
+      const unsigned lo = NT <= TEHMM_FUSED_2W ? __builtin_amdgcn_readfirstlane(rlo) : rlo;
+      const unsigned hi = NT <= TEHMM_FUSED_2W ? __builtin_amdgcn_readfirstlane(rhi) : rhi;
+      const unsigned long long rbu = ((unsigned long long)hi << 32) | lo;
+      prow[r] = (unsigned long long)(size_t)post + rbu * 8ull;
+      prun |= (int)__builtin_amdgcn_readfirstlane(rhi) >= 0 ? 1u << r : 0u;       // (the mask is scalar in every form)
+    }
+    psink = (unsigned long long)(size_t)(sink + ((int64_t)__builtin_amdgcn_readfirstlane(tile) << 6));
+  }
+  // Slot k (0 .. KS) of the stores of one tile: store the rows that slot k - 1 read, read rows 16 k / KS .. 16 (k + 1) / KS
+  // - 1 -- one MFMA group covers the LDS latency.  `mk`: prun, or 0 when the tile holds no posterior row (a warm-up
+  // step, or nothing yet); `so`: the producing step's s N.  Always 16 global stores per tile, whatever the step.
+  constexpr int RPS = (16 + KS - 1) / KS;                  // rows per slot, at most
+  double pval[RPS];
+#pragma unroll
+  for (int i = 0; i < RPS; ++i) pval[i] = 0.0;
+  auto post_slot = [&](int k, unsigned mk, int so) {
+    const unsigned voff = (unsigned)(so + pcol) * 8u;
+    const unsigned long long sadj = psink - (unsigned long long)so * 8ull;
+    if (k > 0) {
+#pragma unroll
+      for (int r = 16 * (k - 1) / KS; r < 16 * k / KS; ++r) {
+        const unsigned long long base = ((mk >> r) & 1u) ? prow[r] : sadj;
+        *(__attribute__((address_space(1))) double *)(size_t)(base + voff) = pval[r - 16 * (k - 1) / KS];   // (GLOBAL:
+      }                                                                                  //  flat stores drain vmcnt)
+    }
+    if (k < KS) {
+#pragma unroll
+      for (int r = 16 * k / KS; r < 16 * (k + 1) / KS; ++r)
+        pval[r - 16 * k / KS] = *(lds_f64 *)(size_t)(pread + (unsigned)(r * NT * 8));
+    }
+  };
   double q[KS], ms;
   EmisStream<NT, LOGDOM> es(ft, fused_lds, win, kq);
   es.begin(L + 2 * Wu - 1);
@@ -677,7 +736,7 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
   es.finish(N, q, ms);
   es.begin(max(L + 2 * Wu - 2, 0));
 #ifdef TEHMM_STAMPS
-  unsigned long long stq[4] = {0, 0, 0, 0}, stt = stamp_now();
+  unsigned long long stq[5] = {0, 0, 0, 0, 0}, stt = stamp_now();
 #define FST(i) do { const unsigned long long n_ = stamp_now(); stq[i] += n_ - stt; stt = n_; } while (0)
 #else
 #define FST(i)
@@ -700,12 +759,22 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
 #pragma unroll
       for (int p = 0; p < (KS + 1) / 2; ++p) alp[p] = ar[(int64_t)p * 64];
     }
+    // the tile in LDS is that of step s + 1 (nothing at the first iteration): its rows leave between the MFMAs below
+    unsigned pmk = s + 1 < L ? prun : 0u;                  // (a scalar select, then opaque: on a condition it can see the
+    if constexpr (DEFER) asm volatile("" : "+s"(pmk));     //  compiler splits the stores into two branchy versions)
+    const int pso = (s + 1) * N;
+    (void)pmk, (void)pso;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(tf[rt][k], v[k], acc[rt], 0, 0, 0);
       es.slot(k);
+      if constexpr (DEFER) post_slot(k, pmk, pso);
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (DEFER) {
+      post_slot(KS, pmk, pso);
+      __builtin_amdgcn_sched_barrier(0);                   // (the last store leaves here, not somewhere in the tail)
     }
     FST(0);
     // (the alpha' row is USED here, unconditionally as far as the compiler can tell: its wait sits behind the MFMA loop)
@@ -768,6 +837,7 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
       for (int k = 0; k < KS; ++k) q[k] = qn[k];
     }
     es.begin(max(s - 2 + Wu, 0));         // next step's gather: its first loads go out ahead of the stores below
+    FST(2);                               // (normalisation | store section)
     // The stores of a step are UNCONDITIONAL and always the same number (round 4): masked elements -- padding columns,
     // items that are not run, the warm-up steps -- go to a per-wave sink (ESTEP: to the row of position L - 1, which the
     // first official step overwrites; rows of items that are not run are rewritten by the exact chain).  Behind a
@@ -788,35 +858,38 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
                                     : make_float2(0.f, 0.f);
         }
       } else {
+        // (DEFER: only the tile is written here, zeros at a warm-up step; post_slot stores it one step later)
 #pragma unroll
         for (int k = 0; k < KS; ++k) *(lds_f64 *)(size_t)(ptile + (unsigned)(((lane & 15) * NT + kq + 4 * k) * 8)) = g[k];
-        int lane_v = lane;                                   // (opaque: keeps the per-store index arithmetic inside
-        asm volatile("" : "+v"(lane_v));                     //  the step instead of 27 hoisted registers)
-        double *const snk = sink + ((int64_t)tile << 6) + lane;
-        int offv = off ? 1 : 0;                              // (opaque and per lane: as a uniform condition the compiler
-        asm volatile("" : "+v"(offv));                       //  splits the nine stores into two branchy versions)
-        // all LDS reads of the step first, then the stores (read - wait - store nine times over cost nine LDS round
-        // trips in a row: 2.7 of the 5.6 thousand cycles this tail took)
-        constexpr int NJ = (16 * NT + 63) / 64;
-        double val[NJ];
-        long long rbase[NJ];
+        if constexpr (!DEFER) {
+          int lane_v = lane;                                   // (opaque: keeps the per-store index arithmetic inside
+          asm volatile("" : "+v"(lane_v));                     //  the step instead of 27 hoisted registers)
+          double *const snk = sink + ((int64_t)tile << 6) + lane;
+          int offv = off ? 1 : 0;                              // (opaque and per lane: as a uniform condition the compiler
+          asm volatile("" : "+v"(offv));                       //  splits the nine stores into two branchy versions)
+          // all LDS reads of the step first, then the stores (read - wait - store nine times over cost nine LDS round
+          // trips in a row: 2.7 of the 5.6 thousand cycles this tail took)
+          constexpr int NJ = (16 * NT + 63) / 64;
+          double val[NJ];
+          long long rbase[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int e = 64 * j + lane_v;                     // element of the [16][NT] tile, row-major
-          const int ec = (16 * NT % 64 == 0 || e < 16 * NT) ? e : 0;
-          const int r = (ec * (65536 / NT + 1)) >> 16;       // e / NT (e < 16 NT <= 1024)
-          val[j] = *(lds_f64 *)(size_t)(ptile + (unsigned)ec * 8u);
-          rbase[j] = *(lds_i64 *)(size_t)(pinfo + (unsigned)r * 8u);
-        }
+          for (int j = 0; j < NJ; ++j) {
+            const int e = 64 * j + lane_v;                     // element of the [16][NT] tile, row-major
+            const int ec = (16 * NT % 64 == 0 || e < 16 * NT) ? e : 0;
+            const int r = (ec * (65536 / NT + 1)) >> 16;       // e / NT (e < 16 NT <= 1024)
+            val[j] = *(lds_f64 *)(size_t)(ptile + (unsigned)ec * 8u);
+            rbase[j] = *(lds_i64 *)(size_t)(pinfo + (unsigned)r * 8u);
+          }
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int e = 64 * j + lane_v;
-          const int ec = (16 * NT % 64 == 0 || e < 16 * NT) ? e : 0;
-          const int r = (ec * (65536 / NT + 1)) >> 16, c = ec - r * NT;
-          const bool real = (offv != 0) & (rbase[j] >= 0) & (c < N) & (16 * NT % 64 == 0 || e < 16 * NT);
-          double *dst = real ? post + (rbase[j] + (int64_t)s * N + c) : snk;
-          asm volatile("" : "+v"(dst));                      // (ONE store through the selected pointer, no branches;
-          *(__attribute__((address_space(1))) double *)dst = val[j];   //  a GLOBAL store: flat ones drain vmcnt)
+          for (int j = 0; j < NJ; ++j) {
+            const int e = 64 * j + lane_v;
+            const int ec = (16 * NT % 64 == 0 || e < 16 * NT) ? e : 0;
+            const int r = (ec * (65536 / NT + 1)) >> 16, c = ec - r * NT;
+            const bool real = (offv != 0) & (rbase[j] >= 0) & (c < N) & (16 * NT % 64 == 0 || e < 16 * NT);
+            double *dst = real ? post + (rbase[j] + (int64_t)s * N + c) : snk;
+            asm volatile("" : "+v"(dst));                      // (ONE store through the selected pointer, no branches;
+            *(__attribute__((address_space(1))) double *)dst = val[j];   //  a GLOBAL store: flat ones drain vmcnt)
+          }
         }
       }
       if (off && run) {
@@ -827,14 +900,20 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
         }
       }
     }
-    FST(2);
+    FST(4);
     ms = msn;
   }
   (void)ms;
+  if constexpr (DEFER) {                                   // flush: the tile of step 0
+    unsigned pmk = L > 0 ? prun : 0u;
+    asm volatile("" : "+s"(pmk));
+#pragma unroll
+    for (int k = 0; k <= KS; ++k) post_slot(k, pmk, 0);
+  }
   if (run) vec_out(end);
 #ifdef TEHMM_STAMPS
   if (lane == 0 && blockIdx.x < 4096)
-    for (int i = 0; i < 4; ++i) g_stamps[4096 * 16 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + i] = stq[i];
+    for (int i = 0; i < 5; ++i) g_stamps[4096 * 16 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + i] = stq[i];
 #endif
 #undef FST
 }

@@ -4763,7 +4763,7 @@ int tehmm_estep_batch(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {
 #ifdef TEHMM_STAMPS
-  if (!out || n <= 0 || n > 2 * 4096 * 16) return fail(TEHMM_ERR_ARG, "tehmm_debug_read_stamps: bad argument");
+  if (!out || n <= 0 || (size_t)n > sizeof(g_stamps) / sizeof(g_stamps[0])) return fail(TEHMM_ERR_ARG, "tehmm_debug_read_stamps: bad argument");
   HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n * sizeof(unsigned long long)));
   return TEHMM_OK;
 #else

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic (not part of the product): where a wave of k_fused_fwd spends its cycles per step.
+"""Diagnostic (not part of the product): where a wave of k_fused_fwd / k_fused_bwd spends its cycles per step.
   python tools/stamps_fused.py --build     (libtehmm_hip_diag.so with -DTEHMM_STAMPS -DTEHMM_DEV_NT=36)
   python tools/stamps_fused.py [Mb]"""
 import ctypes, os, subprocess, sys
@@ -27,12 +27,19 @@ hb = HipBatch(obs.data_ptr(), offs, device_ptrs=True, K=model.n_tracks)
 for _ in range(2):
     hm.eval(hb, viterbi=False, posterior=True)
 print({k: round(v, 2) for k, v in hb.timing().items()})
-n = 2 * 4096 * 16
+n = 3 * 4096 * 16
 buf = (ctypes.c_uint64 * n)()
 _lib.check(_lib.load().tehmm_debug_read_stamps(buf, n), "stamps")
 steps = 512 + 64
-for name, a in zip(("forward", "backward"), np.frombuffer(buf, dtype=np.uint64).reshape(2, 4096, 4, 4).astype(np.float64)):
-    a = a[a.sum(axis=(1, 2)) > 0]
-    print(name, "waves", a.shape[0] * 4, "cycles per step: mfma+slots %.0f  finish %.0f  tail %.0f  stores+loop %.0f  total %.0f"
-          % tuple(list(a.mean(axis=(0, 1)) / steps) + [a.sum(axis=2).mean() / steps]))
+raw = np.frombuffer(buf, dtype=np.uint64).astype(np.float64)
+# forward: four stages per wave; backward: five (the tail split into normalisation and store section) in eight slots
+fwd = raw[:4096 * 16].reshape(4096, 4, 4)
+bwd = raw[4096 * 16:].reshape(4096, 4, 8)[:, :, :5]
+fwd = fwd[fwd.sum(axis=(1, 2)) > 0]
+bwd = bwd[bwd.sum(axis=(1, 2)) > 0]
+print("forward waves", fwd.shape[0] * 4, "cycles per step: mfma+slots %.0f  finish %.0f  tail %.0f  stores+loop %.0f  total %.0f"
+      % tuple(list(fwd.mean(axis=(0, 1)) / steps) + [fwd.sum(axis=2).mean() / steps]))
+m = bwd.mean(axis=(0, 1)) / steps
+print("backward waves", bwd.shape[0] * 4, "cycles per step: mfma+slots %.0f  finish %.0f  tail: normalisation %.0f + store section %.0f"
+      "  loop top %.0f  total %.0f" % (m[0], m[1], m[2], m[4], m[3], bwd.sum(axis=2).mean() / steps))
 hb.close(); hm.close()
