@@ -371,6 +371,39 @@ int tehmm_compare_lds_labels(void);
 /* Intervals per workgroup of the run merge's count and scatter passes. */
 int64_t tehmm_compare_block_items(void);
 
+/* ---- Target site duplications (bin/tsdFinder.py on kmer.py) and the clean-up of bin/removeBedOverlaps.py ------------
+ * tehmm_tsd_find: exact forward matches between the bases left and right of every element, as intervalTsds
+ * (tsdFinder.py:242-298) finds them.  Sequences: n_seq records in one byte buffer, record q = bases[seq_offsets[q],
+ * seq_offsets[q + 1]), upper or lower case.  Elements: seq_index / start / end [n], all host, in output order.
+ * Options as the tool's: min_len (--min, the k-mer length), max_len (--max), left, right, overlap, all (0: the nearest
+ * match of every element only) and max_score (--maxScore; -1: no filter; below -1 keeps nothing).
+ * Out: counts [n] = matches of every element; the matches of all elements in element order, within an element in the
+ * reference's list order, as six columns of *n_out rows: left start / end, d1 = |start - left end|, right start /
+ * end, d2 = |end - right start| (coordinates inside the element's sequence).  On TEHMM_OK *n_out is the number of
+ * matches whatever cap is, and the first min(*n_out, cap) rows of the columns are written (cap 0: the columns may be
+ * NULL; call again with cap >= *n_out).  On an error *n_out is 0.
+ * Checked before any device call: TEHMM_ERR_ARG for a NULL pointer, n_seq < 1, n < 1, cap < 0, min_len < 1,
+ * min_len > max_len, min_len > 21 (hashDNA asserts there), decreasing seq_offsets, and the first element with a
+ * seq_index outside [0, n_seq), start < 0 or start > end; TEHMM_ERR_UNSUPPORTED for n > 2^31 - 1 and for a search
+ * window above tehmm_tsd_window() = 64 bases (left + overlap - 1 or right + overlap - 1).  Checked on the device:
+ * TEHMM_ERR_ARG naming the lowest element with a base other than ACGTNacgtn inside a window that is searched (the
+ * reference asserts there); bases outside every searched window are never read. */
+int tehmm_tsd_find(int n_seq, const uint8_t *bases, const int64_t *seq_offsets, int64_t n, const int32_t *seq_index,
+                   const int64_t *start, const int64_t *end, int min_len, int max_len, int left, int right, int overlap,
+                   int max_score, int all, int32_t *counts, int64_t cap, int64_t *left_start, int64_t *left_end,
+                   int64_t *d1, int64_t *right_start, int64_t *right_end, int64_t *d2, int64_t *n_out);
+/* removeBedOverlaps.py:76-95 on a list sorted by (chrom_id, start): start = max(start, end of the last kept interval
+ * of the chromosome), kept iff end > start.  Out: out_index (position in the list) and out_start (the new start) of
+ * the kept intervals, in list order; cap / *n_out as in tehmm_tsd_find.  TEHMM_ERR_ARG for NULL lists, n < 1,
+ * cap < 0 and, from the device, naming the first interval whose chrom_id or (inside a chrom_id) start is below its
+ * predecessor's; TEHMM_ERR_UNSUPPORTED for n > 2^31 - 1. */
+int tehmm_remove_overlaps(int64_t n, const int32_t *chrom_id, const int64_t *start, const int64_t *end, int64_t cap,
+                          int64_t *out_index, int64_t *out_start, int64_t *n_out);
+/* Device time of the passes of the calling thread's last call of the two above, as tehmm_segment_last_timing. */
+int tehmm_tsd_last_timing(int max_entries, const char **names, double *milliseconds);
+/* The longest search window tehmm_tsd_find serves, in bases. */
+int tehmm_tsd_window(void);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

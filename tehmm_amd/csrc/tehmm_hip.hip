@@ -16,6 +16,7 @@
 #include "tehmm_edist.hip.h"
 #include "tehmm_segment.hip.h"
 #include "tehmm_compare.hip.h"
+#include "tehmm_tsd.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4759,6 +4760,7 @@ int tehmm_estep_batch(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double
 #include "tehmm_aux_host.inc"
 #include "tehmm_segment_host.inc"
 #include "tehmm_compare_host.inc"
+#include "tehmm_tsd_host.inc"
 
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {
