@@ -1294,6 +1294,7 @@ struct EvalKnobs {
   bool soft_ties;       // TEHMM_SOFT_TIES=0: every rounding tie ends a piece of the quantised pass
   int emis_split;       // TEHMM_EMIS_SPLIT: three-wave emission + gain pass on (1) / off (0); -1: by batch size
   int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
+  int gain_window;      // TEHMM_GAIN_WINDOW: positions of an item the gain pass runs on (0: all of them); -1: a quarter
   bool rowindex_ref;    // TEHMM_ROWINDEX_REF=1 (test-only): index records by k_fused_rowindex_ref, the layout's definition
   // 64 <= N <= 128
   bool wide;            // TEHMM_WIDE=0: the one-wave sequential kernels instead of the four-wave ones (k_*_wide)
@@ -1330,6 +1331,7 @@ static EvalKnobs read_eval_knobs() {
   k.soft_ties = num("TEHMM_SOFT_TIES", 1) != 0;
   k.emis_split = std::getenv("TEHMM_EMIS_SPLIT") ? (num("TEHMM_EMIS_SPLIT", 0) != 0 ? 1 : 0) : -1;
   k.defer = num("TEHMM_DEFER", -1);
+  k.gain_window = std::getenv("TEHMM_GAIN_WINDOW") ? std::max(0, num("TEHMM_GAIN_WINDOW", 0)) : -1;
   k.rowindex_ref = num("TEHMM_ROWINDEX_REF", 0) != 0;
   k.wide = num("TEHMM_WIDE", 1) != 0;
   k.wide_cp = num("TEHMM_WIDE_CP", 1) != 0;
@@ -1745,14 +1747,14 @@ static int ensure_qtabs(tehmm_model *m, bool ratio) {
 
 // Binade placement and the work list of the quantised pass on the device, in stream order behind the gain pass
 // (tehmm_place.hip.h).  Returns the upper bound of work units the quantised pass is launched for.
-static int launch_vit_place(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, int CS, bool ratio, hipStream_t st,
-                            int *n_work_max) {
+static int launch_vit_place(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, int CS, int Wn, bool ratio,
+                            hipStream_t st, int *n_work_max) {
   LaneWork &lw = b->lw;
   SpecWork &sw = b->sw;
   const LaneGeom lg = lane_geom(lw);
   hipLaunchKernelGGL(k_vit_place_chunks, dim3(std::max(1, b->n)), dim3(64), 0, st, iv, (const int64_t *)sw.first.p,
                      (const int64_t *)sw.t0.p, (const int64_t *)lw.ifirst.p, b->n, CS, lw.L, (const double *)lw.vgain.p,
-                     (const int *)m->qok[ratio ? 1 : 0].p, kSpecMarginRel, kSpecCross ? 1 : 0, sw.e.p,
+                     (const double *)lw.slog32.p, Wn, (const int *)m->qok[ratio ? 1 : 0].p, kSpecMarginRel, kSpecCross ? 1 : 0, sw.e.p,
                      sw.gain.p);
   const int gb = (lw.n_groups + 255) / 256;
   hipLaunchKernelGGL(k_vit_place_count, dim3(std::max(1, gb)), dim3(256), 0, st, lg, (const int64_t *)sw.first.p,
@@ -1793,10 +1795,15 @@ static void launch_emis_lane(tehmm_batch *b, const tehmm_model *m, const Interva
                      want_f32 ? lw.B32.p : (float *)nullptr);
 }
 
+// whether the three-wave form of the emission + gain pass runs (see launch_emis_gain_lane); emis_split: the knob
+static bool emis_gain_split(int NT, int n_groups, int emis_split) {
+  return NT >= 12 && (emis_split >= 0 ? emis_split != 0 : n_groups < 2048);
+}
+
 // emission rows (fp64 log rows for the exact Viterbi pass) and P0 in one pass
 template <int NT>
 static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em,
-                                  int CS, int Wu, bool ratio, int emis_split, hipStream_t st) {
+                                  int CS, int Wu, int Wn, bool ratio, int emis_split, hipStream_t st) {
   LaneWork &lw = b->lw;
   // round 4: the states of a row split over the three waves of a unit (tehmm_lane3.hip.h); TEHMM_EMIS_SPLIT=0 keeps
   // the one-wave kernel (which also serves the smallest models); emis_split: that knob, -1 if not set
@@ -1804,8 +1811,7 @@ static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const In
     // (measured, 36 states: 1.1 Mb 0.98 ms against 1.70; 100 Mb 17.4 against 14.7 -- three waves repeat the observation
     //  decode and the bookkeeping of a position, and a full GPU is short of vector issue slots, not of waves: the split
     //  form serves the batches that leave the one-wave kernel fewer than two waves per SIMD)
-    const bool split = emis_split >= 0 ? emis_split != 0 : lw.n_groups < 2048;
-    if (split) {
+    if (emis_gain_split(NT, lw.n_groups, emis_split)) {
       constexpr int NW = TEHMM_P2_NW, NU = 2;
       const size_t lds3 = Emis3Geom<NT, NW, NU>::lds_bytes(em.lds_rows);
       const dim3 grid3((lw.n_groups + NU - 1) / NU);
@@ -1825,13 +1831,21 @@ static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const In
   if constexpr (NT <= TEHMM_RATIO_LANE_MAX) if (ratio) {
     allow_lds(k_emis_gain_lane<NT, true>, lds);
     hipLaunchKernelGGL((k_emis_gain_lane<NT, true>), dim3((lw.n_groups + 3) / 4), dim3(256), lds, st, iv, em,
-                       lane_geom(lw), m->N, CS, Wu, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
+                       lane_geom(lw), m->N, CS, Wu, 0, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
                        (const double *)b->ratios.p);
+    return;
+  }
+  if (Wn > 0) {
+    // the gain over the last Wn positions of every item only (EvalPlan::gain_window)
+    allow_lds(k_emis_gain_lane<NT, false, true>, lds);
+    hipLaunchKernelGGL((k_emis_gain_lane<NT, false, true>), dim3((lw.n_groups + 3) / 4), dim3(256), lds, st, iv, em,
+                       lane_geom(lw), m->N, CS, Wu, Wn, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
+                       (const double *)nullptr);
     return;
   }
   allow_lds(k_emis_gain_lane<NT>, lds);
   hipLaunchKernelGGL((k_emis_gain_lane<NT>), dim3((lw.n_groups + 3) / 4), dim3(256), lds, st, iv, em, lane_geom(lw),
-                     m->N, CS, Wu, (const float *)m->ltP.p, lw.B.p, lw.vgain.p, (const double *)nullptr);
+                     m->N, CS, Wu, 0, (const float *)m->ltP.p, lw.B.p, lw.vgain.p, (const double *)nullptr);
 }
 
 template <int NT>
@@ -2770,6 +2784,11 @@ struct EvalPlan {
   // pass needs besides the gains is put on the stream BEFORE the gain pass
   bool dev_place;
   int WuV;                // Viterbi warm-up of the lane passes: 32 (a multiple of 32), at most LS
+  // The gain pass on the last gain_window positions of every item only (0: on all of them), the rest of an item's gain
+  // from the forward pass's log-scale records (tehmm_place.hip.h: place_item_gain).  Only where those records exist
+  // ahead of the placement and the one-wave emission kernel runs: split_post, device placement, no segment ratios,
+  // items of at least 128 positions.  Knob, else a quarter of the item (a multiple of 32).
+  int gain_window;
   // Order of the posterior against the Viterbi pipeline (knob, else by size): 0 none; 1 behind the Viterbi passes;
   // 3 (fused lane passes) the forward half from the start, beside the emission-row kernel and the binade placement,
   // the quantised pass behind the forward pass, the backward half behind it, next to the exact chain.
@@ -2834,7 +2853,17 @@ static int plan_lanes(EvalPlan &p, const tehmm_model *m, tehmm_batch *b, const E
   p.defer_post = p.vit && p.postr && p.vspec && (p.defer_mode == 1 || p.defer_mode == 3);
   p.split_post = p.defer_post && p.defer_mode == 3 && p.flane && p.fused_fb && p.vlane;
   p.wide_defer = p.vit && p.postr && !p.vspec && !p.coop && p.defer_mode != 0;
+  p.gain_window = 0;                                  // (plan_gain_window, once lane_prepare has counted the groups)
   return TEHMM_OK;
+}
+
+// EvalPlan::gain_window, behind lane_prepare: which emission kernel runs depends on the number of item groups.  A window
+// that leaves no room for the warm-up inside the item (or TEHMM_GAIN_WINDOW=0) keeps the full pass.
+static void plan_gain_window(EvalPlan &p, const tehmm_model *m, const tehmm_batch *b, const EvalKnobs &kn) {
+  if (!(p.split_post && p.dev_place && p.emis_gain && !p.ratio && p.LS >= 128 && p.LS % 32 == 0)) return;
+  if (emis_gain_split(m->NP, b->lw.n_groups, kn.emis_split)) return;
+  const int wn = (kn.gain_window >= 0 ? kn.gain_window : p.LS / 4) / 32 * 32;
+  if (wn > 0 && wn + p.WuV <= p.LS) p.gain_window = wn;
 }
 
 // What the stages of one call share.
@@ -2888,7 +2917,7 @@ static int eval_emis_p0(EvalCtx &c) {
     // emission rows of every position, once, item-interleaved (log rows for Viterbi, linear for fwd/bwd)
     if (p.emis_gain) {
       nt_dispatch(m->NP, [&](auto nt) {
-        launch_emis_gain_lane<nt>(b, m, c.iv, c.em, p.CS, p.WuV, p.ratio, c.kn.emis_split, st);
+        launch_emis_gain_lane<nt>(b, m, c.iv, c.em, p.CS, p.WuV, p.gain_window, p.ratio, c.kn.emis_split, st);
       });
     } else {
       nt_dispatch(m->NP, [&](auto nt) {
@@ -3174,9 +3203,11 @@ static int eval_viterbi(EvalCtx &c) {
     const bool soft = c.kn.soft_ties;
     if (p.dev_place) {
       int n_work_max = 0;
-      rc = launch_vit_place(b, m, iv, p.CS, p.ratio, st, &n_work_max);
+      // (a windowed gain pass: the placement reads the forward pass's log-scale records as well)
+      if (p.split_post && p.gain_window) (void)hipStreamWaitEvent(st, b->evX[1], 0);
+      rc = launch_vit_place(b, m, iv, p.CS, p.gain_window, p.ratio, st, &n_work_max);
       if (rc) return rc;
-      if (p.split_post) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
+      if (p.split_post && !p.gain_window) (void)hipStreamWaitEvent(st, b->evX[1], 0);     // the forward pass itself is through
       nt_dispatch(m->NP, [&](auto nt) {
         launch_vit_lane<nt>(b, m, iv, c.vc, p.ratio, soft, p.WuV, n_work_max, (const double *)m->qall[p.ratio ? 1 : 0].p,
                             TEHMM_SPEC_MIN_E, (const int *)&lw.place.p->n_work, st);
@@ -3345,6 +3376,7 @@ static int eval_counters(const EvalCtx &c) {
 #endif
     add("count:viterbi_exact_blocks", st[0]);
     add("count:viterbi_chunk_jumps", st[1]);
+    add("count:gain_window", c.p.gain_window);
   }
   return TEHMM_OK;
 }
@@ -3390,6 +3422,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   if (p.vlane || p.flane || p.glane) {
     rc = lane_prepare(b, m, p.CS, p.LS, p.flane, p.vlane, p.glane, p.fused_fb, !p.emis_gain);
     if (rc) return rc;
+    plan_gain_window(p, m, b, kn);
   }
   if (p.flane) {
     rc = fb_warmup(b, m, p.LS, c.iv, c.emg, kn, &c.WuF);

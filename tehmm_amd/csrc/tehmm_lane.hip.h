@@ -1171,12 +1171,16 @@ __global__ __launch_bounds__(256) void k_vit_gain_lane(IntervalTab iv, LaneGeom 
 // into the packed-float max-plus recurrence of P0 -- starting Wu positions early for the warm-up (those rows
 // are recomputed, not stored: + Wu / L work).  Outputs: B (fp64 log rows, item-interleaved; NaN rows where no
 // state can emit) and gain[item] as k_vit_gain_lane.
+// WIN (Wn a multiple of 32, Wn + Wu <= L): P0 runs on the last Wn positions of the item only, warmed up on the Wu rows of
+// the item before them -- no row is computed twice -- and gain[item] is the gain over that window; the placement
+// completes it with the forward pass's log-scale records (tehmm_place.hip.h: place_item_gain).  P0 is 55 % of this
+// kernel's vector instructions and no result depends on it.  Rows, NaN marking and the NaN gain are the full pass's.
 // ------------------------------------------------------------------------------------------
-template <int NT, bool RATIO = false>
+template <int NT, bool RATIO = false, bool WIN = false>
 #ifndef TEHMM_EMIS_WAVES
 #define TEHMM_EMIS_WAVES 2
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TEHMM_EMIS_WAVES, TEHMM_EMIS_WAVES))) void k_emis_gain_lane(IntervalTab iv, EmisTab em, LaneGeom lg, int N, int CS, int Wu,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TEHMM_EMIS_WAVES, TEHMM_EMIS_WAVES))) void k_emis_gain_lane(IntervalTab iv, EmisTab em, LaneGeom lg, int N, int CS, int Wu, int Wn,
                                                         const float *__restrict__ tabf, double *B, double *gain,
                                                         const double *__restrict__ ratios = nullptr) {
   extern __shared__ double emis_ltab[];
@@ -1195,7 +1199,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TEHMM_EMIS_
   const int maxlen = wave_max_i32(len);
   const int64_t ct0 = (t0 / CS) * CS;
   const bool run = valid && ct0 > 0 && ct0 + CS <= T;       // P0 runs on full chunks but an interval's first
-  const int s_first = __any(run) ? -Wu : 0;
+  // windowed P0 (0 < Wn < L): the recurrence starts from zeros at s_p0 = L - Wn - Wu inside the item -- its warm-up
+  // rows are the item's own, nothing is recomputed -- and the pass leaves the gain over the item's last Wn positions
+  // (WIN is a template argument so that the full pass keeps its single basic block per position)
+  const int s_first = WIN ? 0 : (__any(run) ? -Wu : 0);
+  const int s_p0 = WIN ? L - Wn - Wu : s_first, s_g0 = WIN ? L - Wn : 0;
   const double qnan = __longlong_as_double(0x7ff8000000000000LL);
   lane_f2 W[NT / 2];
 #pragma unroll
@@ -1223,9 +1231,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TEHMM_EMIS_
 #pragma unroll
       for (int j = 0; j < NT; ++j) B[o + ((int64_t)j << 6)] = good ? x[j] : qnan;
     }
-    // ---- P0 step on the row rounded to float (see k_vit_gain_lane)
-    if (s == 0) g0 = vec_max();
     bad = bad | (act && !good);
+    if (WIN && s < s_p0) continue;                        // (wave-uniform: W still holds its zeros at s_p0)
+    // ---- P0 step on the row rounded to float (see k_vit_gain_lane)
+    if (s == s_g0) g0 = vec_max();
     int z = 0;
     asm volatile("" : "+s"(z));
     const_f2 *tp = (const_f2 *)(size_t)tabf + z;

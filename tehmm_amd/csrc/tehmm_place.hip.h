@@ -45,6 +45,22 @@ __device__ __forceinline__ double place_wave_scan(double v, int lane) {
   return v;
 }
 
+// The Viterbi gain of an item.  Wn = 0: the gain pass ran over the whole item and igain holds it.  Otherwise igain holds
+// g_w, the float max-plus gain over the item's last Wn positions only (k_emis_gain_lane<.., WIN>), and the forward pass
+// supplies the rest: slog32 [item][L / 32] is its cumulative log-scale since the item's start at every 32nd position,
+// so with dF(a, b) the forward score's change over [a, b)
+//   gain ~= dF(0, L) + (g_w - dF(L - Wn, L)) * L / Wn.
+// Only the Viterbi-minus-forward difference is extrapolated from the window; it is small against either score and
+// stationary (tools/gain_window_sim.py), where the gain itself is not.  A NaN in either source gives NaN.
+__device__ __forceinline__ double place_item_gain(const double *__restrict__ igain, const double *__restrict__ slog32,
+                                                  int64_t item, int L, int Wn) {
+  const double gw = igain[item];
+  if (Wn <= 0) return gw;
+  const int R = L / 32;
+  const double f1 = slog32[item * R + R - 1], f0 = slog32[item * R + (L - Wn) / 32 - 1];
+  return f1 + (gw - (f1 - f0)) * ((double)L / (double)Wn);
+}
+
 // One wave per interval: item gains -> chunk gains (a chunk the lanes did not run, i.e. the interval's first and its
 // ragged tail, gets the interval's mean gain per position; a full chunk whose item failed stays NaN and ends the
 // placement of everything behind it), prefix sums, binade per chunk.  qok[e - MIN_E] = 0: the quantised table of that
@@ -52,6 +68,7 @@ __device__ __forceinline__ double place_wave_scan(double v, int lane) {
 __global__ __launch_bounds__(64) void k_vit_place_chunks(IntervalTab iv, const int64_t *__restrict__ cfirst,
                                                          const int64_t *__restrict__ ct0, const int64_t *__restrict__ ifirst,
                                                          int n_iv, int CS, int LS, const double *__restrict__ igain,
+                                                         const double *__restrict__ slog32, int Wn,
                                                          const int *__restrict__ qok, double rel, int cross, int *e_out,
                                                          double *cgain_out) {
   const int i = blockIdx.x, lane = threadIdx.x;
@@ -70,7 +87,7 @@ __global__ __launch_bounds__(64) void k_vit_place_chunks(IntervalTab iv, const i
       if (full && c != c0) {
         const int64_t it0 = ifirst[i] + t0 / LS;
         g = 0.0;
-        for (int k = 0; k < SUB; ++k) g += igain[it0 + k];
+        for (int k = 0; k < SUB; ++k) g += place_item_gain(igain, slog32, it0 + k, LS, Wn);
       }
       cgain_out[c] = g;
       if (g == g) { sum += g; cnt += 1.0; }
