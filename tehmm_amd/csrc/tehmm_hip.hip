@@ -474,6 +474,29 @@ struct tehmm_batch {
   std::vector<double> tms;
 };
 
+// Stage times of a call: reset_timings at its start, add_stage(name, slot, slot) of b->ev[] while it is enqueued,
+// stage_times once its streams are through; counters (name, value) are appended behind the times.
+static void reset_timings(tehmm_batch *b) {
+  b->tnames.clear();
+  b->tpairs.clear();
+  b->tms.clear();
+}
+static void add_stage(tehmm_batch *b, const char *name, int e0, int e1) {
+  b->tnames.push_back(name);
+  b->tpairs.push_back({e0, e1});
+}
+static void stage_times(tehmm_batch *b) {
+  for (auto &pr : b->tpairs) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, b->ev[pr.first], b->ev[pr.second]);
+    b->tms.push_back((double)ms);
+  }
+}
+static void add_counter(tehmm_batch *b, const char *name, double v) {
+  b->tnames.push_back(name);
+  b->tms.push_back(v);
+}
+
 // All tehmm_* functions below are declared extern "C" in include/tehmm_hip.h.
 
 int tehmm_abi_version(void) { return 4; }
@@ -2724,25 +2747,17 @@ static int eval_large(tehmm_model *m, tehmm_batch *b, int flags, double *viterbi
                                                        b->tstate, b->last_state.p, b->paths.p, st);
     if (rc) return rc;
     (void)hipEventRecord(b->ev[2], st);
-    b->tnames.push_back("k_vit_large");
-    b->tpairs.push_back({0, 1});
-    b->tnames.push_back("traceback");
-    b->tpairs.push_back({1, 2});
+    add_stage(b, "k_vit_large", 0, 1);
+    add_stage(b, "traceback", 1, 2);
   }
   if (postr) {
-    b->tnames.push_back("k_fwd_large");
-    b->tpairs.push_back({5, 6});
-    b->tnames.push_back("k_bwd_large");
-    b->tpairs.push_back({6, 7});
+    add_stage(b, "k_fwd_large", 5, 6);
+    add_stage(b, "k_bwd_large", 6, 7);
   }
   HIPCHK(hipGetLastError());
   if (vit) HIPCHK(hipStreamSynchronize(b->sV));
   if (postr) HIPCHK(hipStreamSynchronize(b->sP));
-  for (auto &pr : b->tpairs) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, b->ev[pr.first], b->ev[pr.second]);
-    b->tms.push_back((double)ms);
-  }
+  stage_times(b);
   if (vit && viterbi_logprob)
     HIPCHK(hipMemcpy(viterbi_logprob, b->vit_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
   if (postr) {
@@ -2960,6 +2975,16 @@ static void eval_emission(EvalCtx &c) {
   (void)hipEventRecord(b->ev[eP + 4], st);
 }
 
+// chunk tables of the fused / lane forward and backward passes
+static FbChunks fb_chunks(const SpecWork &sw, const LaneWork &lw, int CS) {
+  FbChunks fc{};
+  fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = CS;
+  fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
+  fc.link_f = lw.link_f.p; fc.glog_f = lw.glog_f.p; fc.link_b = lw.link_b.p; fc.runend_f = lw.runend_f.p;
+  fc.pre_f = lw.cpre_f.p; fc.runstart_b = lw.runstart_b.p;
+  return fc;
+}
+
 // half (fused passes only): 1 = the forward half now, 2 = the backward half; 0 = everything
 static int eval_posterior(EvalCtx &c, int half) {
   tehmm_batch *b = c.b;
@@ -2975,11 +3000,7 @@ static int eval_posterior(EvalCtx &c, int half) {
   if (p.flane) {
     // lane = item passes (forward, backward, links), then the two sequential chains on the
     // item-interleaved rows, then the transposing combine
-    FbChunks fc{};
-    fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = p.CS;
-    fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
-    fc.link_f = lw.link_f.p; fc.glog_f = lw.glog_f.p; fc.link_b = lw.link_b.p; fc.runend_f = lw.runend_f.p;
-    fc.pre_f = lw.cpre_f.p; fc.runstart_b = lw.runstart_b.p;
+    const FbChunks fc = fb_chunks(sw, lw, p.CS);
     if (half != 2) {
       (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
       (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
@@ -3304,10 +3325,7 @@ static int eval_viterbi(EvalCtx &c) {
 
 // The stage timings of a call: names and event pairs, Viterbi stages first.
 static void eval_timings(const EvalPlan &p, tehmm_batch *b) {
-  auto add = [&](const char *name, int e0, int e1) {
-    b->tnames.push_back(name);
-    b->tpairs.push_back({e0, e1});
-  };
+  auto add = [&](const char *name, int e0, int e1) { add_stage(b, name, e0, e1); };
   if (p.vit) {
     if (p.vlane || p.glane) {
       add("emission_rows", eV, eV + 4);
@@ -3339,21 +3357,23 @@ static void eval_timings(const EvalPlan &p, tehmm_batch *b) {
   }
 }
 
+// 64-position blocks the exact forward / backward chains ran, chunks they could jump over
+static int add_chain_counters(tehmm_batch *b) {
+  int st[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpy(st, b->sw.stats.p + 2, sizeof(st), hipMemcpyDeviceToHost));
+  add_counter(b, "count:forward_exact_blocks", st[0]);
+  add_counter(b, "count:forward_chunk_jumps", st[1]);
+  add_counter(b, "count:backward_exact_blocks", st[2]);
+  add_counter(b, "count:backward_chunk_jumps", st[3]);
+  return TEHMM_OK;
+}
+
 // counters (not times) behind the timings, once both streams are through
 static int eval_counters(const EvalCtx &c) {
   tehmm_batch *b = c.b;
-  auto add = [&](const char *name, double v) {
-    b->tnames.push_back(name);
-    b->tms.push_back(v);
-  };
-  if (c.p.fspec) {
-    int st[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(st, b->sw.stats.p + 2, sizeof(st), hipMemcpyDeviceToHost));
-    add("count:forward_exact_blocks", st[0]);
-    add("count:forward_chunk_jumps", st[1]);
-    add("count:backward_exact_blocks", st[2]);
-    add("count:backward_chunk_jumps", st[3]);
-  }
+  auto add = [&](const char *name, double v) { add_counter(b, name, v); };
+  if (c.p.fspec)
+    if (int rc = add_chain_counters(b)) return rc;
   if (c.wide_cp) add("count:wide_chunk_parallel_warmup", b->ww.wu_ok);
   if (c.wide_vit) {
     int st2[2] = {0, 0};
@@ -3388,9 +3408,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   if (!(flags & (TEHMM_EVAL_VITERBI | TEHMM_EVAL_POSTERIOR)))
     return fail(TEHMM_ERR_ARG, "tehmm_eval_batch: nothing to do");
   b->map_valid = false;
-  b->tnames.clear();
-  b->tpairs.clear();
-  b->tms.clear();
+  reset_timings(b);
   if (b->n == 0 || b->total == 0) return TEHMM_OK;
   if (m->large) return eval_large(m, b, flags, viterbi_logprob, forward_logprob);
 #ifdef TEHMM_DEV_NT
@@ -3487,11 +3505,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
   HIPCHK(hipGetLastError());
   if (p.vit) HIPCHK(hipStreamSynchronize(b->sV));
   if (p.postr) HIPCHK(hipStreamSynchronize(b->sP));
-  for (auto &pr : b->tpairs) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, b->ev[pr.first], b->ev[pr.second]);
-    b->tms.push_back((double)ms);
-  }
+  stage_times(b);
   rc = eval_counters(c);
   if (rc) return rc;
   if (p.vit && viterbi_logprob)
@@ -4106,690 +4120,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
   return TEHMM_OK;
 }
 
-// ---- fused Baum-Welch E-step ---------------------------------------------------------------
-namespace {
-constexpr int kEstepChunk = 512;
-
-template <int NT>
-void launch_estep(const tehmm_model *m, const IntervalTab &iv, const EmisTab &em, bool ratio, int n_iv,
-                  int n_chunks, EstepWork &w, const double *tratios, hipStream_t st) {
-  constexpr int CPB = NT <= 44 ? 64 : 32;
-  const EmisTab emf = n_iv > 256 ? without_lds_tables(em) : em;
-  size_t lds = ((size_t)4 * CPB * (NT + 1) + 4 * CPB + 5 * NT + (size_t)emf.lds_rows * NT) * sizeof(double);
-  size_t lds2 = (size_t)std::max(1, m->lds_rows) * NT * sizeof(double) + (size_t)3 * m->K * sizeof(int) + 16;
-  if (ratio) {
-    allow_lds(k_fb_coop<NT, CPB, true>, lds);
-    hipLaunchKernelGGL((k_fb_coop<NT, CPB, true>), dim3(n_iv), dim3(256), lds, st, iv, emf, m->N, m->A.p,
-                       m->lt.p, m->pi.p, tratios, w.alpha.p, w.beta.p, w.fwd_lp.p, w.dead.p, w.wrows.p,
-                       w.escale.p);
-    allow_lds(k_estep_accum<NT, true>, lds2);
-    hipLaunchKernelGGL((k_estep_accum<NT, true>), dim3((n_chunks + 3) / 4), dim3(256), lds2, st, iv, em,
-                       m->N, kEstepChunk, w.chunk_iv.p, w.chunk_t0.p, n_chunks, w.alpha.p, w.beta.p,
-                       w.wrows.p, w.escale.p, w.C, w.D, w.start, w.stat);
-  } else {
-    allow_lds(k_fb_coop<NT, CPB, false>, lds);
-    hipLaunchKernelGGL((k_fb_coop<NT, CPB, false>), dim3(n_iv), dim3(256), lds, st, iv, emf, m->N, m->A.p,
-                       m->lt.p, m->pi.p, (const double *)nullptr, w.alpha.p, w.beta.p, w.fwd_lp.p,
-                       w.dead.p, w.wrows.p, w.escale.p);
-    allow_lds(k_estep_accum<NT, false>, lds2);
-    hipLaunchKernelGGL((k_estep_accum<NT, false>), dim3((n_chunks + 3) / 4), dim3(256), lds2, st, iv, em,
-                       m->N, kEstepChunk, w.chunk_iv.p, w.chunk_t0.p, n_chunks, w.alpha.p, w.beta.p,
-                       w.wrows.p, w.escale.p, w.C, w.D, w.start, w.stat);
-  }
-}
-}  // namespace
-
-
-// ---- chunk-parallel E-step on the fused posterior passes (tehmm_estep.hip.h) -----------------------------
-// Track partition of the reduction kernels (tehmm_estep.hip.h): tracks of at most TEHMM_ESTEP_SMALL rows are
-// packed into 16-row tiles for the one-hot product on the matrix cores, the others into LDS histogram groups of
-// at most `cap_rows` rows (first fit, decreasing).
-// Where the split lies (measured, config-4 model, 50 Mb, reduce stage): tracks of <= 9 rows on the matrix cores
-// 21.6 ms, <= 21 rows 17.2, <= 31 (all ten small tracks) 16.3 -- a 16-row tile costs 12 matrix instructions per
-// 16-item tile and step (~9 ns per row and CU), a track in LDS ~190-270 ns (nine ds_add_f64 at ~1 lane per cycle,
-// more when items share a symbol), and the LDS kernel's workgroups do not share a CU with the 416-register waves
-// of the one-hot kernel, so the two add up rather than overlap: break-even near 40 rows.
-// TEHMM_ESTEP_SMALL overrides (largest track, in rows, that takes the one-hot product): EvalKnobs::estep_small.
-static void estep_build_groups(const tehmm_model *m, int cap_rows, int small, EstepGroups &eg) {
-  std::memset(&eg, 0, sizeof(eg));
-  std::vector<int> big;
-  int row = 0;
-  for (int i = 0; i < TEHMM_ESTEP_MAXRT * 16; ++i) eg.rt_info[i] = -1;
-  for (int k = 0; k < m->K; ++k) {
-    if (m->rowcnt[k] <= small && row + m->rowcnt[k] <= TEHMM_ESTEP_MAXRT * 16) {
-      for (int sy = 0; sy < m->rowcnt[k]; ++sy, ++row) {
-        eg.rt_info[row] = (k & 255) | (sy << 8);
-        eg.rt_grow[row] = m->rowbase[k] + sy;
-      }
-    } else {
-      big.push_back(k);
-    }
-  }
-  eg.n_rt = (row + 15) / 16;
-  std::stable_sort(big.begin(), big.end(), [&](int a, int b2) { return m->rowcnt[a] > m->rowcnt[b2]; });
-  std::vector<std::vector<int>> bins;
-  std::vector<int> load;
-  for (int k : big) {
-    size_t g = 0;
-    while (g < bins.size() && load[g] + m->rowcnt[k] > cap_rows) ++g;
-    if (g == bins.size()) { bins.emplace_back(); load.push_back(0); }
-    bins[g].push_back(k);
-    load[g] += m->rowcnt[k];
-  }
-  int slot = 0;
-  eg.n_lds = (int)bins.size();
-  for (size_t g = 0; g < bins.size(); ++g) {
-    eg.first[g] = slot;
-    int lrow = 0;
-    for (int k : bins[g]) {
-      eg.info[slot] = (k & 127) | ((m->rowcnt[k] & 511) << 7) | (lrow << 16);
-      eg.gbase[slot] = m->rowbase[k];
-      lrow += m->rowcnt[k];
-      ++slot;
-    }
-    eg.rows[g] = lrow;
-  }
-  eg.first[bins.size()] = slot;
-}
-
-static bool estep_fused_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio, const EvalKnobs &kn) {
-  const int CS = kn.spec_chunk;
-  if (!kn.estep_fused) return false;
-  if (ratio || m->N >= 64 || m->NP > 64 || CS <= 0 || b->total < 2 * (int64_t)CS) return false;
-  if (!m->ptab.p || m->K > 78 || m->K > 127) return false;
-  for (int k = 0; k < m->K; ++k)
-    if (m->rowcnt[k] > 511) return false;
-  return true;
-}
-
-template <int NT>
-static int launch_estep_reduce(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, double *dev_stats,
-                               hipStream_t st) {
-  LaneWork &lw = b->lw;
-  EstepWork &w = b->ew;
-  const LaneGeom lg = lane_geom(lw);
-  const EstepGroups &eg = w.h_groups;
-  const int64_t n_tiles = (int64_t)lw.n_groups * 4;
-  double *gC = dev_stats + stats_off_C(m->NP), *gstart = dev_stats + stats_off_start(),
-         *gstat = dev_stats + stats_off_stat(m->NP);
-  // the three reductions are independent: the LDS-atomic histograms (LDS pipe) run next to the two matrix-core
-  // products on their own streams.  Every writer owns a slot of a partial buffer; the fold kernels add the slots in
-  // order (tehmm_estep.hip.h: reproducible sums).
-  (void)hipEventRecord(b->evX[0], st);
-  const int gxm = (int)std::max<int64_t>(1, std::min<int64_t>((n_tiles + 3) / 4, 512));
-  const int cells_xi = NT * NT + NT;
-  HIPCHK(w.part_xi.ensure((size_t)gxm * 4 * cells_xi));
-  int gx = 0, gxh = 0, max_rows = 0, tot_rows = 0;
-  if (eg.n_lds > 0) {
-    for (int g = 0; g < eg.n_lds; ++g) { max_rows = std::max(max_rows, eg.rows[g]); tot_rows += eg.rows[g]; }
-    const size_t lds = (size_t)max_rows * NT * sizeof(double) + (size_t)m->K * sizeof(int) + 16;
-    allow_lds(k_estep_hist_lds<NT>, lds);
-    gx = (int)std::max<int64_t>(1, std::min<int64_t>((n_tiles + 7) / 8, 256));
-    HIPCHK(w.part_lds.ensure((size_t)gx * tot_rows * NT));
-    // positions one workgroup can add into one cell: its tiles x 16 items x L
-    const int64_t per_wg = ((n_tiles + (int64_t)gx * 8 - 1) / ((int64_t)gx * 8)) * 8 * 16 * (int64_t)lw.L;
-    int shift = 62;
-    while (shift > 20 && (double)per_wg * std::ldexp(1.0, shift) >= 9.2e18) --shift;
-    (void)hipStreamWaitEvent(b->sV, b->evX[0], 0);
-    hipLaunchKernelGGL((k_estep_hist_lds<NT>), dim3(gx, eg.n_lds), dim3(512), lds, b->sV, iv, lg,
-                       (const EstepGroups *)w.d_groups.p, m->N, b->KP, (const uint8_t *)b->obs.p,
-                       (const float *)lw.GAM32.p, w.part_lds.p, shift);
-    hipLaunchKernelGGL(k_estep_fold_lds, dim3((max_rows * NT + 255) / 256, eg.n_lds), dim3(256), 0, b->sV,
-                       (const double *)w.part_lds.p, gx, m->N, NT, (const EstepGroups *)w.d_groups.p, gstat);
-    (void)hipEventRecord(b->ev[11], b->sV);
-  }
-  if (eg.n_rt > 0) {
-    constexpr int RTG = EstepGeom<NT>::RTG;
-    (void)hipStreamWaitEvent(b->sB, b->evX[0], 0);
-    gxh = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, 768));     // one tile per workgroup at a time, 3 per CU
-    HIPCHK(w.part_rt.ensure((size_t)gxh * eg.n_rt * 16 * NT));
-    hipLaunchKernelGGL((k_estep_hist_mfma<NT>), dim3(gxh, (eg.n_rt + RTG - 1) / RTG), dim3(TEHMM_ESTEP_HW * 64), 0, b->sB, iv, lg,
-                       (const EstepGroups *)w.d_groups.p, m->N, b->KP, (const uint8_t *)b->obs.p,
-                       (const float *)lw.GAM32.p, w.part_rt.p);
-    hipLaunchKernelGGL(k_estep_fold_rows, dim3((eg.n_rt * 16 * NT + 255) / 256), dim3(256), 0, b->sB,
-                       (const double *)w.part_rt.p, gxh, m->N, NT, (const EstepGroups *)w.d_groups.p, gstat);
-    (void)hipEventRecord(b->evX[1], b->sB);
-  }
-  hipLaunchKernelGGL((k_estep_xi<NT>), dim3(gxm), dim3(256), 0, st, iv, lg, m->N, (const float *)lw.AL32.p,
-                     (const float *)lw.GAM32.p, (const float *)lw.WZ32.p, w.part_xi.p);
-  hipLaunchKernelGGL(k_estep_fold_xi, dim3((cells_xi + 255) / 256), dim3(256), 0, st, (const double *)w.part_xi.p, gxm * 4,
-                     m->N, NT, gC, gstart);
-  if (eg.n_lds > 0) (void)hipStreamWaitEvent(st, b->ev[11], 0);
-  if (eg.n_rt > 0) (void)hipStreamWaitEvent(st, b->evX[1], 0);
-  return TEHMM_OK;
-}
-
-// returns TEHMM_OK and *done = true when the fused path ran; *done = false: the caller falls back
-static int estep_fused(tehmm_model_t *m, tehmm_batch_t *b, const EvalKnobs &kn, double *dev_stats, double *lp_out, int *dead_out,
-                       bool *done) {
-  *done = false;
-  b->lw.rix_ref = kn.rowindex_ref;
-  const int CS = kn.spec_chunk;
-  if (!estep_fused_wanted(m, b, false, kn)) return TEHMM_OK;
-  const int LS = lane_sub_size(CS, b->total, kn.lane_sub);
-  if (LS <= 0) return TEHMM_OK;
-  LaneWork &lw = b->lw;
-  EstepWork &w = b->ew;
-  if (!(lw.AL32.p && lw.GAM32.p && lw.L == LS && lw.CS == CS && lw.NP == m->NP)) {
-    // three float rows + index records per position must fit; otherwise the grouped sequential path
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(dev_mem_info(&free_b, &total_b));
-    const double per = (double)b->total * (3.0 * 32.0 * al32_pairs(m->NP) + 40.0) * 1.15;
-    if (per > 0.85 * (double)free_b) return TEHMM_OK;
-  }
-  int rc = spec_prepare(b, m, CS);
-  if (rc) return rc;
-  rc = lane_prepare(b, m, CS, LS, true, false, false, true, false);
-  if (rc) return rc;
-  const size_t na = (size_t)std::max(1, lw.n_groups) * LS * 512 * al32_pairs(m->NP);
-  if (!lw.GAM32.p) {
-    HIPCHK(lw.GAM32.alloc(na));
-    HIPCHK(lw.WZ32.alloc(na));
-    HIPCHK(hipMemset(lw.GAM32.p, 0, na * sizeof(float)));      // (slots beyond an interval's end are read, never written)
-    HIPCHK(hipMemset(lw.WZ32.p, 0, na * sizeof(float)));
-  }
-  if (!b->fwd_lp.p || !b->dead.p) {
-    HIPCHK(b->fwd_lp.alloc((size_t)b->n + 1));
-    HIPCHK(b->dead.alloc((size_t)b->n + 1));
-    if (!b->first_good.p) HIPCHK(b->first_good.alloc((size_t)b->n + 1));
-  }
-  if (w.groups_model != m->uid || !w.d_groups.p) {
-    const int cap_rows = (int)((160 * 1024 - (size_t)m->K * sizeof(int) - 64) / ((size_t)m->NP * sizeof(double)));
-    estep_build_groups(m, cap_rows, kn.estep_small, w.h_groups);
-    HIPCHK(w.d_groups.upload(&w.h_groups, 1));
-    w.groups_model = m->uid;
-  }
-  IntervalTab iv;
-  EmisTab em;
-  fill_tabs(m, b, iv, em, false);
-  SpecWork &sw = b->sw;
-  int WuF = 64;
-  rc = fb_warmup(b, m, LS, iv, without_lds_tables(em), kn, &WuF);
-  if (rc) return rc;
-  FbChunks fc{};
-  fc.iv = sw.iv.p; fc.t0 = sw.t0.p; fc.first = sw.first.p; fc.n = sw.n_chunks; fc.CS = CS;
-  fc.scale = sw.scale.p; fc.wstart = sw.wstart.p;
-  fc.link_f = lw.link_f.p; fc.glog_f = lw.glog_f.p; fc.link_b = lw.link_b.p; fc.runend_f = lw.runend_f.p;
-  fc.pre_f = lw.cpre_f.p; fc.runstart_b = lw.runstart_b.p;
-  hipStream_t st = b->sP;
-  b->tnames.clear();
-  b->tpairs.clear();
-  b->tms.clear();
-  (void)hipEventRecord(b->ev[10], st);
-  (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
-  (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
-  int rcf = TEHMM_OK;
-  nt_dispatch(m->NP, [&](auto nt) { rcf = launch_fused_fb<nt>(b, m, iv, em, fc, WuF, st, b->ev[8], b->ev[6], true); });
-  if (rcf) return rcf;
-  (void)hipEventRecord(b->ev[7], st);
-  int rcr = TEHMM_OK;
-  nt_dispatch(m->NP, [&](auto nt) { rcr = launch_estep_reduce<nt>(b, m, iv, dev_stats, st); });
-  if (rcr) return rcr;
-  (void)hipEventRecord(b->ev[9], st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  static const struct { const char *name; int a, b2; } stages[] = {
-      {"estep_forward_pass", 10, 8}, {"estep_backward_pass", 8, 6}, {"estep_backward_chain", 6, 7}, {"estep_reduce", 7, 9}};
-  for (const auto &sg : stages) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, b->ev[sg.a], b->ev[sg.b2]);
-    b->tnames.push_back(sg.name);
-    b->tms.push_back((double)ms);
-  }
-  {
-    int cnt[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(cnt, sw.stats.p + 2, sizeof(cnt), hipMemcpyDeviceToHost));
-    static const char *names[4] = {"count:forward_exact_blocks", "count:forward_chunk_jumps",
-                                   "count:backward_exact_blocks", "count:backward_chunk_jumps"};
-    for (int i = 0; i < 4; ++i) {
-      b->tnames.push_back(names[i]);
-      b->tms.push_back((double)cnt[i]);
-    }
-  }
-  std::vector<double> lp((size_t)b->n);
-  std::vector<int> dead((size_t)b->n);
-  HIPCHK(hipMemcpy(lp.data(), b->fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(dead.data(), b->dead.p, (size_t)b->n * sizeof(int), hipMemcpyDeviceToHost));
-  double lp_total = 0.0;
-  int dead_any = 0;
-  for (int id = 0; id < b->n; ++id) {
-    if (b->h_len[(size_t)id] <= 0) continue;
-    lp_total += lp[(size_t)id];
-    dead_any |= dead[(size_t)id];
-    b->h_fwd_lp[(size_t)id] = dead[(size_t)id] ? std::nan("") : lp[(size_t)id];
-  }
-  *lp_out = lp_total;
-  *dead_out = dead_any;
-  *done = true;
-  return TEHMM_OK;
-}
-
-// ---- E-step on the item-parallel passes of tehmm_wide.hip.h (tehmm_wide_estep.hip.h): 64 <= N <= 128 states, and
-// segment ratios at any N <= 128 ---------------------------------------------------------------------------------
-static bool estep_wide_wanted(const tehmm_model *m, const tehmm_batch *b, bool ratio, const EvalKnobs &kn) {
-  const int mode = kn.estep_wide;                   // 0: off, 1: where the fused passes do not apply, 2: everywhere
-  if (mode == 0 || m->N > 128 || b->total < 1024) return false;
-  if (mode == 1 && !(ratio || m->N >= 64)) return false;
-  if (m->K > 255) return false;
-  return true;
-}
-
-template <int NPW>
-static int launch_wide_estep_reduce(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const LaneGeom &lg, bool ratio,
-                                    const EvalKnobs &kn, double *dev_stats, hipStream_t st) {
-  WideWork &w = b->ww;
-  using G = WideEstepGeom<NPW>;
-  const int64_t n_tiles = ((int64_t)w.n_items + 15) / 16;
-  double *gC = dev_stats + stats_off_C(m->NP), *gD = dev_stats + stats_off_D(m->NP), *gstart = dev_stats + stats_off_start(),
-         *gstat = dev_stats + stats_off_stat(m->NP);
-  // work units = item tiles x SQ position ranges: at least ~4096 of them (a 2 Mb batch has 1000 item tiles; the GPU
-  // 1024 SIMDs), ranges of 16 positions or more
-  int SQ = 1;
-  while (SQ < 8 && n_tiles * SQ < 4096 && w.L / (2 * SQ) >= 16 && w.L % (2 * SQ) == 0) SQ *= 2;
-  if (kn.wide_estep_sq >= 1 && w.L % kn.wide_estep_sq == 0) SQ = kn.wide_estep_sq;
-  const int64_t n_units = n_tiles * SQ;
-  // xi: two workgroups per CU at most; gamma product: one unit per workgroup at a time, partial buffer <= 128 MB
-  const int gxm = (int)std::max<int64_t>(1, std::min<int64_t>((n_units + G::TPW - 1) / G::TPW, 512));
-  HIPCHK(w.part_xi.ensure((size_t)gxm * G::TPW * NPW * NPW));
-  const int nrt = w.h_rows.n_rt;
-  const int64_t slot_rows = (int64_t)nrt * 16 * NPW * 8;
-  // gamma product: four units per workgroup at a time (one per wave), up to three row tiles per wave; partial buffer <= 128 MB
-  const int rtw = std::min(nrt, NPW <= 64 ? 4 : 3);      // (every group of row tiles reads the gamma rows once more)
-  const int gxr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((n_units + 3) / 4, 256), std::max<int64_t>(64, ((int64_t)32 << 20) / slot_rows)));
-  HIPCHK(w.part_rows.ensure((size_t)gxr * 4 * nrt * 16 * NPW));
-  // the products are independent: the gamma product and the LDS histograms run on their own streams next to the xi
-  // product (TEHMM_WIDE_ESTEP_SERIAL=1: one after the other, for profiling)
-  const bool serial = kn.wide_estep_serial;
-  hipStream_t sB = serial ? st : b->sB, sV = serial ? st : b->sV;
-  (void)hipEventRecord(b->evX[0], st);
-  (void)hipStreamWaitEvent(sB, b->evX[0], 0);
-  {
-    const dim3 gr(gxr, (nrt + rtw - 1) / rtw);
-#define ROWS(R_, W_)                                                                                                    \
-    hipLaunchKernelGGL((k_wide_estep_rows<NPW, R_, W_>), gr, dim3(256), 0, sB, iv, lg, (const WideRows *)w.d_rows.p, b->KP, \
-                       (const uint8_t *)b->obs.p, (const double *)(R_ ? b->ratios.p : nullptr), (const float *)w.GAM.p,  \
-                       w.part_rows.p, SQ)
-    if constexpr (NPW <= 64) {
-      if (rtw == 4) { if (ratio) ROWS(true, 4); else ROWS(false, 4); }
-    }
-    if (rtw < 4) {
-      if (ratio) { if (rtw == 1) ROWS(true, 1); else if (rtw == 2) ROWS(true, 2); else ROWS(true, 3); }
-      else { if (rtw == 1) ROWS(false, 1); else if (rtw == 2) ROWS(false, 2); else ROWS(false, 3); }
-    }
-#undef ROWS
-  }
-  hipLaunchKernelGGL(k_wide_fold_rows, dim3((nrt * 16 * m->N + 255) / 256), dim3(256), 0, sB, (const double *)w.part_rows.p,
-                     gxr * 4, m->N, NPW, m->NP, (const WideRows *)w.d_rows.p, gstat, gstart, gD);
-  (void)hipEventRecord(b->evX[1], sB);
-  if (w.h_lds.n_trk > 0) {
-    // tracks with many symbols: fixed-point histograms privatised in LDS, on a third stream
-    const int nsplit = w.lds_nsplit, HS = NPW / nsplit;
-    int max_rows = 0, tot_rows = 0;
-    for (int t = 0; t < w.h_lds.n_trk; ++t) { max_rows = std::max(max_rows, w.h_lds.rows[t]); tot_rows += w.h_lds.rows[t]; }
-    const size_t lds = (size_t)max_rows * HS * sizeof(unsigned long long);
-    const int gxl = (int)std::max<int64_t>(1, std::min<int64_t>((n_units + 7) / 8, 256));
-    HIPCHK(w.part_lds.ensure((size_t)gxl * tot_rows * NPW));
-    // the largest sum one workgroup can reach in a cell: its units x 16 items x L / SQ positions x the largest ratio
-    const int64_t per_wg = ((n_units + (int64_t)gxl * 8 - 1) / ((int64_t)gxl * 8)) * 8 * 16 * (int64_t)(w.L / SQ);
-    const double vmax = (double)per_wg * (ratio ? std::max(1.0, w.ratio_max) : 1.0);
-    int shift = 62;
-    while (shift > 20 && vmax * std::ldexp(1.0, shift) >= 9.2e18) --shift;
-    (void)hipStreamWaitEvent(sV, b->evX[0], 0);
-    const dim3 gl(gxl, w.h_lds.n_trk * nsplit);
-#define LDSK(NS_, R_)                                                                                                  \
-    do {                                                                                                               \
-      allow_lds(k_wide_estep_hist_lds<NPW, NS_, R_>, lds);                                                             \
-      hipLaunchKernelGGL((k_wide_estep_hist_lds<NPW, NS_, R_>), gl, dim3(512), lds, sV, iv, lg,                     \
-                         (const WideLds *)w.d_lds.p, m->N, b->KP, (const uint8_t *)b->obs.p,                           \
-                         (const double *)(R_ ? b->ratios.p : nullptr), (const float *)w.GAM.p, w.part_lds.p, shift, SQ); \
-    } while (0)
-    if (nsplit == 1) { if (ratio) LDSK(1, true); else LDSK(1, false); }
-    else { if (ratio) LDSK(2, true); else LDSK(2, false); }
-#undef LDSK
-    hipLaunchKernelGGL(k_wide_fold_lds, dim3((max_rows * HS + 255) / 256, w.h_lds.n_trk * nsplit), dim3(256), 0, sV,
-                       (const double *)w.part_lds.p, gxl, m->N, m->NP, HS, nsplit, (const WideLds *)w.d_lds.p, gstat);
-    (void)hipEventRecord(b->ev[11], sV);
-  }
-  hipLaunchKernelGGL((k_wide_estep_xi<NPW>), dim3(gxm), dim3(256), 0, st, iv, lg, (const float *)w.AL.p, (const float *)w.WZ.p,
-                     w.part_xi.p, SQ);
-  hipLaunchKernelGGL(k_wide_fold_xi, dim3((m->N * m->N + 255) / 256), dim3(256), 0, st, (const double *)w.part_xi.p, gxm * G::TPW,
-                     m->N, NPW, m->NP, gC);
-  (void)hipStreamWaitEvent(st, b->evX[1], 0);
-  if (w.h_lds.n_trk > 0) (void)hipStreamWaitEvent(st, b->ev[11], 0);
-  return TEHMM_OK;
-}
-
-// returns TEHMM_OK and *done = true when the path ran; *done = false: the caller falls back
-static int estep_wide(tehmm_model_t *m, tehmm_batch_t *b, const EvalKnobs &kn, bool ratio, double *dev_stats, double *lp_out,
-                      int *dead_out, bool *done) {
-  *done = false;
-  if (!estep_wide_wanted(m, b, ratio, kn)) return TEHMM_OK;
-  const int NPW = wide_npw<TEHMM_WIDE_ESTEP_WIDTHS>(m->N);
-  if (NPW <= 0) return TEHMM_OK;
-  WideWork &w = b->ww;
-  if (!w.h_flags) HIPCHK(hipHostMalloc((void **)&w.h_flags, 64, hipHostMallocDefault));
-  const int L = wide_item_length(b, kn);
-  if (!(w.GAM.p && w.L == L && w.NPW == NPW)) {
-    // emission rows + three float rows per position must fit
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(dev_mem_info(&free_b, &total_b));
-    if ((double)b->total * NPW * 22.0 + (double)(b->total / L + b->n + 64) * NPW * 40.0 > 0.85 * (double)free_b) return TEHMM_OK;
-  }
-  {
-    bool fits = true;
-    if (int rcg = wide_geometry(b, NPW, L, &fits)) return rcg;
-    if (!fits) return TEHMM_OK;
-  }
-  const size_t na = (size_t)std::max(1, w.n_groups) * 64 * L * (NPW / 4) * 4;
-  if (!w.GAM.p) {
-    HIPCHK(w.GAM.alloc(na));
-    HIPCHK(w.WZ.alloc(na));
-    w.al_zeroed = false;
-  }
-  if (!w.al_zeroed) {       // slots no pass writes (beyond an item's end) are read by the reductions: zero once
-    HIPCHK(hipMemset(w.AL.p, 0, na * sizeof(float)));
-    HIPCHK(hipMemset(w.GAM.p, 0, na * sizeof(float)));
-    HIPCHK(hipMemset(w.WZ.p, 0, na * sizeof(float)));
-    w.al_zeroed = true;
-  }
-  if (!b->fwd_lp.p || !b->dead.p) {
-    HIPCHK(b->fwd_lp.alloc((size_t)b->n + 1));
-    HIPCHK(b->dead.alloc((size_t)b->n + 1));
-    if (!b->first_good.p) HIPCHK(b->first_good.alloc((size_t)b->n + 1));
-  }
-  if (w.rows_model != m->uid || w.rows_npw != NPW || !w.d_rows.p) {
-    // tracks of more than TEHMM_ESTEP_SMALL rows whose histogram [rows][NPW or NPW / 2] fits a CU's LDS go there,
-    // the others (and START / DIAG) through the one-hot product
-    WideRows &wr = w.h_rows;
-    WideLds &wl = w.h_lds;
-    std::memset(&wl, 0, sizeof(wl));
-    for (int i = 0; i < TEHMM_ESTEP_MAXRT * 16; ++i) { wr.info[i] = -1; wr.grow[i] = 0; }
-    const int small = kn.estep_small;
-    constexpr size_t kLdsCap = 150 * 1024;
-    int big_rows = 0;
-    for (int k = 0; k < m->K; ++k)
-      if (m->rowcnt[k] > small) big_rows = std::max(big_rows, m->rowcnt[k]);
-    w.lds_nsplit = (size_t)big_rows * NPW * 8 <= kLdsCap ? 1 : 2;
-    int row = 0;
-    wr.info[row++] = TEHMM_WIDE_ROW_START;
-    wr.info[row++] = TEHMM_WIDE_ROW_DIAG;
-    for (int k = 0; k < m->K; ++k) {
-      const bool to_lds = m->rowcnt[k] > small && (size_t)m->rowcnt[k] * (NPW / w.lds_nsplit) * 8 <= kLdsCap;
-      if (to_lds) {
-        wl.col[wl.n_trk] = k;
-        wl.rows[wl.n_trk] = m->rowcnt[k];
-        wl.gbase[wl.n_trk] = m->rowbase[k];
-        ++wl.n_trk;
-        continue;
-      }
-      for (int sy = 0; sy < m->rowcnt[k]; ++sy, ++row) {
-        if (row >= TEHMM_ESTEP_MAXRT * 16) return TEHMM_OK;        // (more rows than the row table holds: fall back)
-        wr.info[row] = (k & 255) | (sy << 8);
-        wr.grow[row] = m->rowbase[k] + sy;
-      }
-    }
-    wr.n_rt = (row + 15) / 16;
-    HIPCHK(w.d_rows.upload(&wr, 1));
-    HIPCHK(w.d_lds.upload(&wl, 1));
-    w.rows_model = m->uid;
-    w.rows_npw = NPW;
-  }
-  if (ratio && w.h_lds.n_trk > 0 && w.ratio_max <= 0.0) {
-    // the fixed-point scale of the LDS histograms needs the largest ratio of the batch (once per batch)
-    if (!w.d_rmax.p) HIPCHK(w.d_rmax.alloc(1));
-    HIPCHK(hipMemset(w.d_rmax.p, 0, sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_ratio_max, dim3(grid_for(b->total_pad, 256, 2048)), dim3(256), 0, b->sP, (const double *)b->ratios.p,
-                       b->total_pad, w.d_rmax.p);
-    unsigned long long bits = 0;
-    HIPCHK(hipMemcpyAsync(&bits, w.d_rmax.p, sizeof(bits), hipMemcpyDeviceToHost, b->sP));
-    HIPCHK(hipStreamSynchronize(b->sP));
-    double rmax = 0.0;
-    std::memcpy(&rmax, &bits, sizeof(rmax));
-    if (!(rmax < 1e12)) return TEHMM_OK;             // (inf / NaN ratios: the sequential kernels own their semantics)
-    w.ratio_max = std::max(rmax, 1e-300);
-  }
-  IntervalTab iv;
-  EmisTab em;
-  fill_tabs(m, b, iv, em, ratio);     // fit applies the ratios to emissions too (basehmm.py:510)
-  const LaneGeom lg = wide_lane_geom(w);
-  hipStream_t st = b->sP;
-  b->tnames.clear();
-  b->tpairs.clear();
-  b->tms.clear();
-  (void)hipEventRecord(b->ev[10], st);
-  HIPCHK(hipMemsetAsync(w.flags.p, 0, 4 * sizeof(int), st));
-  launch_wide_emis(b, m, iv, em, lg, ratio ? 3 : 2, nullptr, st);
-  (void)hipEventRecord(b->ev[12], st);
-  (void)hipEventRecord(b->ev[9], st);
-  if (int rc = wide_post_attempt(b, m, iv, kn, wide_first_warmup(w, m, kn, false), st, b->ev[8], true)) return rc;
-  WideRetries re = {b->ev[9], b->ev[6], 1};
-  bool verified = false;
-  if (int rc = wide_verdict(b, m, iv, kn, st, b->ev[8], true, &re, &verified)) return rc;
-  if (!verified) return TEHMM_OK;                      // the caller falls back
-  int rcr = TEHMM_OK;
-  nt_dispatch_of<TEHMM_WIDE_ESTEP_WIDTHS>(NPW, [&](auto npw) { rcr = launch_wide_estep_reduce<npw>(b, m, iv, lg, ratio, kn, dev_stats, st); });
-  if (rcr) return rcr;
-  (void)hipEventRecord(b->ev[7], st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  // stage times (forward / backward: of the LAST attempt)
-  static const struct { const char *name; int a, b2; } stages[] = {
-      {"estep_emission_rows", 10, 12}, {"estep_forward_pass", 9, 8}, {"estep_backward_pass", 8, 6}, {"estep_reduce", 6, 7}};
-  for (const auto &sg : stages) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, b->ev[sg.a], b->ev[sg.b2]);
-    b->tnames.push_back(sg.name);
-    b->tms.push_back((double)ms);
-  }
-  b->tnames.push_back("count:wide_estep_attempts");
-  b->tms.push_back((double)re.attempts);
-  b->tnames.push_back("count:wide_estep_warmup");
-  b->tms.push_back((double)w.wu_ok);
-  std::vector<double> lp((size_t)b->n);
-  HIPCHK(hipMemcpy(lp.data(), b->fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
-  double lp_total = 0.0;
-  for (int id = 0; id < b->n; ++id) {
-    if (b->h_len[(size_t)id] <= 0) continue;
-    lp_total += lp[(size_t)id];
-    b->h_fwd_lp[(size_t)id] = lp[(size_t)id];
-  }
-  *lp_out = lp_total;
-  *dead_out = 0;
-  *done = true;
-  return TEHMM_OK;
-}
-
-// Raw statistics of every interval of the batch ADDED into dev_stats (device buffer of
-// stats_size(NP, R) doubles, layout in tehmm_aux.hip.h); *dead_any: some interval met an impossible row
-// after its first emittable one (the reference's lattices are NaN there).
-static int estep_accumulate(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double *dev_stats, double *lp_out,
-                            int *dead_out) {
-#ifdef TEHMM_DEV_NT
-  if (m->N < 64 && m->NP != TEHMM_DEV_NT)
-    return fail(TEHMM_ERR_UNSUPPORTED, "development build: fused kernels exist for one padded state count only");
-#endif
-  *lp_out = 0.0;
-  *dead_out = 0;
-  b->h_fwd_lp.assign((size_t)b->n, 0.0);
-  if (b->n == 0 || b->total == 0) return TEHMM_OK;
-  const bool ratio = use_ratios && b->has_ratios;
-  const int N = m->N, NP = m->NP;
-  {
-    bool done = false;
-    const EvalKnobs kn = read_eval_knobs();
-    const bool wide_first = kn.estep_wide == 2;
-    if (!ratio && N < 64 && !wide_first) {
-      int rcf = estep_fused(m, b, kn, dev_stats, lp_out, dead_out, &done);
-      if (rcf) return rcf;
-      if (done) return TEHMM_OK;
-    }
-    int rcw = estep_wide(m, b, kn, ratio, dev_stats, lp_out, dead_out, &done);
-    if (rcw) return rcw;
-    if (done) return TEHMM_OK;
-    if (N >= 64)
-      return fail(TEHMM_ERR_UNSUPPORTED, "E-step at N >= 64: the item-parallel passes do not apply to this batch (impossible "
-                                         "emission rows, links that do not verify, or a batch below 1024 rows): use the array-level path");
-  }
-  // Intervals are processed in groups whose alpha / beta / w rows fit a fixed workspace
-  // (3 x 8N + 4 bytes per position, 40 % of the free HBM): the 3 Gb training sets of config 4
-  // never materialise whole-genome lattices.
-  size_t free_b = 0, total_b = 0;
-  (void)dev_mem_info(&free_b, &total_b);
-  int64_t budget_bytes = (int64_t)((double)(free_b + (size_t)b->ew.rows_cap * (24 * N + 4)) * 0.4);
-  if (budget_bytes < (4ll << 30)) budget_bytes = 4ll << 30;
-  const int64_t budget_rows = std::max<int64_t>(budget_bytes / (24 * N + 4), 1);
-  EstepWork &w = b->ew;
-  if (w.N != N) {
-    w.alpha.release();
-    w.rows_cap = 0;
-    w.N = N;
-  }
-  w.start = dev_stats + stats_off_start();
-  w.C = dev_stats + stats_off_C(NP);
-  w.D = dev_stats + stats_off_D(NP);
-  w.stat = dev_stats + stats_off_stat(NP);
-  IntervalTab iv;
-  EmisTab em;
-  fill_tabs(m, b, iv, em, ratio);     // fit applies the ratios to emissions too (basehmm.py:510)
-  double lp_total = 0.0;
-  int dead_any = 0;
-  size_t pos_in_order = 0;
-  while (pos_in_order < (size_t)b->n) {
-    // next group: consecutive slots of the longest-first order
-    std::vector<int> g_order;
-    std::vector<int64_t> grow0((size_t)b->n, 0);
-    std::vector<int> chunk_iv;
-    std::vector<int64_t> chunk_t0;
-    int64_t rows = 0;
-    while (pos_in_order < (size_t)b->n) {
-      const int id = b->h_order[pos_in_order];
-      const int64_t T = b->h_len[id];
-      if (!g_order.empty() && rows + T > budget_rows) break;
-      g_order.push_back(id);
-      grow0[id] = rows;
-      for (int64_t t0 = 0; t0 < T; t0 += kEstepChunk) {
-        chunk_iv.push_back(id);
-        chunk_t0.push_back(t0);
-      }
-      rows += T;
-      ++pos_in_order;
-    }
-    if (rows == 0) continue;
-    if (rows > w.rows_cap) {
-      HIPCHK(w.alpha.alloc((size_t)rows * N + 1));
-      HIPCHK(w.beta.alloc((size_t)rows * N + 1));
-      HIPCHK(w.wrows.alloc((size_t)rows * N + 1));
-      HIPCHK(w.escale.alloc((size_t)rows + 1));
-      w.rows_cap = rows;
-    }
-    if (b->n > w.n_cap) {
-      HIPCHK(w.fwd_lp.alloc((size_t)b->n + 1));
-      HIPCHK(w.dead.alloc((size_t)b->n + 1));
-      w.n_cap = b->n;
-    }
-    HIPCHK(hipMemset(w.dead.p, 0, (size_t)(b->n + 1) * sizeof(int)));
-    HIPCHK(hipMemset(w.escale.p, 0, ((size_t)rows + 1) * sizeof(int)));
-    HIPCHK(w.order.upload(g_order.data(), g_order.size()));
-    HIPCHK(w.grow0.upload(grow0.data(), grow0.size()));
-    HIPCHK(w.chunk_iv.upload(chunk_iv.data(), chunk_iv.size()));
-    HIPCHK(w.chunk_t0.upload(chunk_t0.data(), chunk_t0.size()));
-    IntervalTab giv = iv;
-    giv.order = w.order.p;
-    giv.out0 = w.grow0.p;
-    const int n_iv = (int)g_order.size(), n_chunks = (int)chunk_iv.size();
-    nt_dispatch(m->NP, [&](auto nt) { launch_estep<nt>(m, giv, em, ratio, n_iv, n_chunks, w, b->ratios.p, b->sP); });
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->sP));
-    std::vector<double> lp((size_t)b->n);
-    std::vector<int> dead((size_t)b->n);
-    HIPCHK(hipMemcpy(lp.data(), w.fwd_lp.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(dead.data(), w.dead.p, (size_t)b->n * sizeof(int), hipMemcpyDeviceToHost));
-    for (int id : g_order) {
-      lp_total += lp[(size_t)id];
-      dead_any |= dead[(size_t)id];
-      b->h_fwd_lp[(size_t)id] = dead[(size_t)id] ? std::nan("") : lp[(size_t)id];
-    }
-  }
-  *lp_out = lp_total;
-  *dead_out = dead_any;
-  return TEHMM_OK;
-}
-
-int64_t tehmm_model_stats_size(const tehmm_model_t *m) {
-  if (m && m->large) return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_stats_size: no device-resident statistics for N > 128");
-  return m ? stats_size(m->NP, m->R) : 0;
-}
-
-int tehmm_estep_batch_device(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double *dev_stats,
-                             double *logprob_sum) {
-  if (!m || !b || !dev_stats || !logprob_sum)
-    return fail(TEHMM_ERR_ARG, "tehmm_estep_batch_device: NULL argument");
-  if (m->K != b->K) return fail(TEHMM_ERR_ARG, "tehmm_estep_batch_device: model/batch track count differ");
-  if (m->N > 128)
-    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch_device: N > 128 (the E-step of such a model runs on the "
-                                       "array-level entry points)");
-  double lp = 0.0;
-  int dead = 0;
-  int rc = estep_accumulate(m, b, use_ratios, dev_stats, &lp, &dead);
-  if (rc) return rc;
-  const double nan = std::nan("");
-  // slots 0 / 1 of the buffer: log-likelihood sum (NaN poisons it, as the reference's NaN lattices would)
-  // and sequence count -- they travel with the statistics through the all-reduce
-  double head[2];
-  HIPCHK(hipMemcpy(head, dev_stats, sizeof(head), hipMemcpyDeviceToHost));
-  head[0] += dead ? nan : lp;
-  head[1] += (double)b->n;
-  HIPCHK(hipMemcpy(dev_stats, head, sizeof(head), hipMemcpyHostToDevice));
-  if (dead) {      // the reference's statistics are NaN from such a sequence on: poison the buffer
-    std::vector<double> bad((size_t)stats_size(m->NP, m->R), nan);
-    bad[1] = head[1];
-    HIPCHK(hipMemcpy(dev_stats, bad.data(), bad.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  *logprob_sum = dead ? nan : lp;
-  return TEHMM_OK;
-}
-
-int tehmm_estep_batch(tehmm_model_t *m, tehmm_batch_t *b, int use_ratios, double *start,
-                      double *trans, double *obsStats, double *logprob_sum) {
-  if (!m || !b || !start || !trans || !obsStats || !logprob_sum)
-    return fail(TEHMM_ERR_ARG, "tehmm_estep_batch: NULL argument");
-  if (m->K != b->K) return fail(TEHMM_ERR_ARG, "tehmm_estep_batch: model/batch track count differ");
-  if (m->N > 128)
-    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_estep_batch: N > 128 (the E-step of such a model runs on the array-level "
-                                       "entry points)");
-  *logprob_sum = 0.0;
-  if (b->n == 0 || b->total == 0) return TEHMM_OK;
-  const int N = m->N, NP = m->NP, K = m->K, S = m->S;
-  EstepWork &w = b->ew;
-  const size_t ssz = (size_t)stats_size(NP, m->R);
-  HIPCHK(w.statbuf.ensure(ssz));
-  HIPCHK(hipMemset(w.statbuf.p, 0, ssz * sizeof(double)));
-  double lp_total = 0.0;
-  int dead_any = 0;
-  int rc = estep_accumulate(m, b, use_ratios, w.statbuf.p, &lp_total, &dead_any);
-  if (rc) return rc;
-  std::vector<double> hs(ssz);
-  HIPCHK(hipMemcpy(hs.data(), w.statbuf.p, ssz * sizeof(double), hipMemcpyDeviceToHost));
-  const double *hS = hs.data() + stats_off_start(), *hC = hs.data() + stats_off_C(NP),
-               *hD = hs.data() + stats_off_D(NP), *hst = hs.data() + stats_off_stat(NP);
-  const double nan = std::nan("");
-  const double invN = 1.0 / (double)N;
-  for (int i = 0; i < N; ++i) {
-    start[i] += dead_any ? nan : hS[i];
-    for (int j = 0; j < N; ++j) {
-      double v = std::exp(m->h_lt[(size_t)i * N + j]) * hC[(size_t)i * NP + j];
-      if (i == j) v += hD[i];
-      trans[(size_t)i * N + j] += dead_any ? nan : v * invN;
-    }
-  }
-  for (int k = 0; k < K; ++k)
-    for (int s2 = 0; s2 < m->rowcnt[k]; ++s2)
-      for (int j = 0; j < N; ++j)
-        obsStats[((size_t)k * N + j) * S + s2] += dead_any ? nan : hst[(size_t)(m->rowbase[k] + s2) * NP + j];
-  *logprob_sum = dead_any ? nan : lp_total;
-  return TEHMM_OK;
-}
-
+#include "tehmm_estep_host.inc"
 #include "tehmm_aux_host.inc"
 #include "tehmm_segment_host.inc"
 #include "tehmm_compare_host.inc"
