@@ -404,6 +404,29 @@ int tehmm_tsd_last_timing(int max_entries, const char **names, double *milliseco
 /* The longest search window tehmm_tsd_find serves, in bases. */
 int tehmm_tsd_window(void);
 
+/* ---- Track loading (trackIO.readBedData / readFastaData) ---------------------------------------------------------
+ * Paints K tracks into data [T, K] (host, row-major, out).  T is the row space of one call: the concatenation of all
+ * tables, records already clipped to their table and shifted into it.  fill [K]: the value of a row nothing covers.
+ * kind [K]: 0 = a track of records, 1 = a track of sequence bytes.
+ * Records of track k are rec_offsets[k] .. rec_offsets[k + 1] of rec_start / rec_end / rec_sym0 / rec_sym, sorted by
+ * rec_start inside the track.  Row p takes its value from the LAST record i of the track with rec_start[i] <= p <
+ * rec_end[i]: rec_sym0[i] when p == rec_start[i], else rec_sym[i] -- what painting the records in order leaves behind.
+ * Sequence tracks own T bytes each of seq_bytes (seq_offsets [K + 1]: 0 bytes for a record track), a byte of 0 standing
+ * for "no base"; row p is seq_lut[q][byte] for the q-th sequence track of the call (seq_lut [number of them][256]).
+ * Checked before any device call: TEHMM_ERR_ARG for NULL pointers, T < 0, K < 1, K > 128, a kind other than 0 / 1,
+ * offsets that do not start at 0 or decrease, a sequence track with records or without its T bytes;
+ * TEHMM_ERR_UNSUPPORTED above 2^31 - 1 records.  Checked on the device: TEHMM_ERR_ARG naming the lowest record index
+ * whose start lies before its predecessor's in the track or that fails 0 <= start < end <= T.  The cost of a row does not
+ * depend on how many records cover it or on their lengths (block maxima of rec_end, fan-out 64). */
+int tehmm_load_tracks_u8(int64_t T, int K, const uint8_t *fill, const uint8_t *kind, const int64_t *rec_offsets,
+                         const int64_t *rec_start, const int64_t *rec_end, const uint8_t *rec_sym0,
+                         const uint8_t *rec_sym, const int64_t *seq_offsets, const uint8_t *seq_bytes,
+                         const uint8_t *seq_lut, uint8_t *data);
+/* Device time of the passes of the calling thread's last tehmm_load_tracks_u8, as tehmm_segment_last_timing. */
+int tehmm_trackio_last_timing(int max_entries, const char **names, double *milliseconds);
+/* Rows of a tile of the paint kernel (tests cross it). */
+int64_t tehmm_trackio_tile_rows(void);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

@@ -72,6 +72,9 @@ SIGNATURES = {
     "tehmm_remove_overlaps": (c_int, [c_i64, i32p, i64p, i64p, c_i64, i64p, i64p, i64p]),
     "tehmm_tsd_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_tsd_window": (c_int, []),
+    "tehmm_load_tracks_u8": (c_int, [c_i64, c_int, u8p, u8p, i64p, i64p, i64p, u8p, u8p, i64p, u8p, u8p, u8p]),
+    "tehmm_trackio_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_trackio_tile_rows": (c_i64, []),
     "tehmm_batch_get_interval_logprobs": (c_int, [vp, f64p]),
     "tehmm_batch_posterior_masksum": (c_int, [vp, f64p, c_i64, c_i64, f64p]),
     "tehmm_batch_map_decode": (c_int, [vp, f64p, f64p]),

@@ -1,0 +1,404 @@
+"""Track file IO: BED and FASTA tracks into per-base uint8 rows (trackIO.py of the reference).
+
+The reference shells out to ``intersectBed | sortBed`` once per track and interval and then assigns every base of every
+record in the interpreter.  Here a file is parsed and sorted once (BedFile), the records of an interval come from binary
+searches, the value map is consulted once per distinct value, and the per-base work -- a "last writer wins" paint -- is
+one device call for all tracks and all intervals (tehmm_load_tracks_u8).  Nothing falls back to a CPU implementation.
+
+The rule, for one track over one table [start, end) of chromosome c:
+  * records: lines starting with '#' are skipped, fields are split on tabs, lines with fewer than 3 fields are skipped;
+  * kept when chrom == c, e > start, s < end and e > s; clipped to oStart = max(start, s), oEnd = min(end, e); sorted
+    stably by oStart (file order among equal clipped starts).  This stands in for ``intersectBed -a file -b interval |
+    sortBed``: bedtools does not define the order among records of equal start, so where such records overlap the
+    reference's result depends on the bedtools build, and this is the order chosen here;
+  * every record gives (sym0, sym) through the value map (valCol, useDelta as trackIO.py:173-203: with useDelta the
+    first base carries the difference to the previous record's value when the two abut, and the rest carries 0);
+  * record r paints sym0 at its first row and sym at the others, in sorted order, over rows that start at the map's
+    missing value.
+FASTA tracks: row i is the map of base start + i of record c (upper-cased unless caseSensitive); rows past the end of
+the sequence keep the missing value.
+
+Differences from the reference, all deliberate: a line's trailing "\\r\\n" is dropped whole (the reference drops one
+character); a value map is required (rows are bytes); a symbol above 255 raises ValueError naming the track (the
+reference's result there depends on the NumPy version); bigWig / bigBed need external tools and raise RuntimeError.
+Not offered: sort= / ignoreBed12= / needIntersect= of readBedData (records are always clipped and sorted here).
+"""
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from ._lib import i64p, ptr, u8p
+
+MAX_SYMBOL = 255
+MAX_TRACKS = 128
+
+
+# ---- BED text ---------------------------------------------------------------------------------------------------------
+def bedRead(path):
+    """The records of a BED file as lists of text fields (trackIO.py:389-404)."""
+    out = []
+    with open(path, "r", newline="") as f:
+        for line in f:
+            if line[:1] == "#":
+                continue
+            fields = line.rstrip("\n").rstrip("\r").split("\t")
+            if len(fields) > 2:
+                out.append(fields)
+    return out
+
+
+def _clip(records, chrom, start, end):
+    """rule step 2 on tuples / lists whose first three fields are chrom, start, end: [(oStart, oEnd, record)]"""
+    kept = [(max(start, int(r[1])), min(end, int(r[2])), r) for r in records
+            if r[0] == chrom and int(r[2]) > start and int(r[1]) < end and int(r[2]) > int(r[1])]
+    kept.sort(key=lambda x: x[0])
+    return kept
+
+
+def readBedIntervals(bedPath, ncol=3, chrom=None, start=None, end=None, sort=False):
+    """Tuples (chrom, start, end[, name[, score]]) of a BED file, or of its part inside chrom:start-end (clipped and
+    sorted by clipped start as in the module docstring).  sort: stable by (chrom, start)."""
+    if not os.path.isfile(bedPath):
+        raise RuntimeError("Bed interval file %s not found" % bedPath)
+    assert ncol in (3, 4, 5)
+    recs = bedRead(bedPath)
+    for r in recs:
+        if len(r) < ncol:
+            raise ValueError("%s: a line has %d fields, ncol = %d" % (bedPath, len(r), ncol))
+    if sort:
+        recs = sorted(recs, key=lambda r: (r[0], int(r[1])))
+    if chrom is not None:
+        assert start is not None and end is not None
+        rows = [(chrom, s, e, r) for s, e, r in _clip(recs, chrom, int(start), int(end))]
+    else:
+        rows = [(r[0], int(r[1]), int(r[2]), r) for r in recs]
+    return [(c, s, e) + tuple(r[3:ncol]) for c, s, e, r in rows]
+
+
+def getMergedBedIntervals(bedPath, ncol=3, sort=False):
+    """Overlapping and abutting intervals merged (what ``bedtools merge`` does by default); like bedtools it wants the
+    file sorted, or sort=True."""
+    if ncol > 3:
+        raise ValueError("getMergedBedIntervals: merged intervals carry no name or score (ncol = %d)" % ncol)
+    out = []
+    for c, s, e in readBedIntervals(bedPath, 3, sort=sort):
+        if out and out[-1][0] == c and s <= out[-1][2]:
+            if e > out[-1][2]:
+                out[-1] = (c, out[-1][1], e)
+        else:
+            out.append((c, s, e))
+    return out
+
+
+class BedFile(object):
+    """A BED file parsed once: per chromosome the records stably sorted by start, with the running maximum of their
+    ends, so that the records of any interval are two binary searches and a short filter."""
+
+    def __init__(self, path):
+        if not os.path.isfile(path):
+            raise RuntimeError("Track file not found %s\n" % path)
+        self.path = path
+        self.fields = bedRead(path)
+        n = len(self.fields)
+        start = np.fromiter((int(r[1]) for r in self.fields), dtype=np.int64, count=n)
+        end = np.fromiter((int(r[2]) for r in self.fields), dtype=np.int64, count=n)
+        groups = dict()
+        for i, r in enumerate(self.fields):
+            groups.setdefault(r[0], []).append(i)
+        self.start, self.end = start, end
+        self.chroms = dict()
+        for c, idx in groups.items():
+            idx = np.asarray(idx, dtype=np.int64)
+            idx = idx[end[idx] > start[idx]]
+            idx = idx[np.argsort(start[idx], kind="stable")]
+            self.chroms[c] = (idx, start[idx], np.maximum.accumulate(end[idx]) if len(idx) else end[idx])
+        self._codes = dict()
+
+    def select(self, chrom, start, end):
+        """(record index, oStart, oEnd) of rule step 2, as int64 arrays"""
+        if chrom not in self.chroms:
+            z = np.zeros(0, dtype=np.int64)
+            return z, z, z
+        idx, s, reach = self.chroms[chrom]
+        first = int(np.searchsorted(reach, start, side="right"))      # nothing before it ends above start
+        lo = int(np.searchsorted(s, start, side="right"))             # [first, lo): clipped start = the table's start
+        hi = int(np.searchsorted(s, end, side="left"))
+        lo = max(min(lo, hi), first)
+        early = idx[first:lo]
+        early = np.sort(early[self.end[early] > start])               # equal clipped starts: file order
+        pick = np.concatenate([early, idx[lo:hi]])
+        return pick, np.maximum(self.start[pick], start), np.minimum(self.end[pick], end)
+
+    def codes(self, col):
+        """(code per record, distinct raw values) of a text column; a record without the column raises"""
+        if col not in self._codes:
+            table = dict()
+            try:
+                code = np.fromiter((table.setdefault(r[col], len(table)) for r in self.fields), dtype=np.int64,
+                                   count=len(self.fields))
+            except IndexError:
+                raise ValueError("%s: a record has no column %d" % (self.path, col))
+            if "" in table:
+                raise ValueError("%s: an empty value in column %d" % (self.path, col))
+            self._codes[col] = (code, list(table))
+        return self._codes[col]
+
+
+def _check_symbols(sym, name):
+    if len(sym) and (sym.max() > MAX_SYMBOL or sym.min() < 0):
+        raise ValueError("track %s: symbol %d does not fit the uint8 table" % (name, int(sym.max())))
+
+
+def recordSymbols(bed, pick, oStart, oEnd, chrom, valCol, valMap, updateValMap, useDelta, name):
+    """rule step 3: (sym0, sym) int64 arrays of the selected records, the map updated in the reference's order"""
+    n = len(pick)
+    if valCol is not None and int(valCol) not in (0, 3, 4):
+        raise ValueError("track %s: valCol is 0, 3 or 4" % name)
+    col = 3 if valCol is None else int(valCol)
+    if not useDelta:
+        if n == 0:
+            z = np.zeros(0, dtype=np.int64)
+            return z, z
+        if col == 0:
+            sym = np.full(n, int(valMap.getMap(1, update=updateValMap)), dtype=np.int64)
+        else:
+            code, values = bed.codes(col)
+            uniq, first, inv = np.unique(code[pick], return_index=True, return_inverse=True)
+            table = np.zeros(len(uniq), dtype=np.int64)
+            for u in np.argsort(first, kind="stable").tolist():      # distinct values in order of first appearance
+                table[u] = int(valMap.getMap(values[int(uniq[u])], update=updateValMap))
+            sym = table[inv.reshape(-1)]
+        _check_symbols(sym, name)
+        return sym, sym
+    return recordSymbolsLoop(bed, pick, oStart, oEnd, chrom, col, valMap, updateValMap, useDelta, name)
+
+
+def recordSymbolsLoop(bed, pick, oStart, oEnd, chrom, col, valMap, updateValMap, useDelta, name):
+    """the reference's per-record loop (trackIO.py:173-203); the vectorised path above must agree with it"""
+    n = len(pick)
+    sym0, sym = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    prevEnd, prevVal = None, 0
+    for x, (i, s, e) in enumerate(zip(pick.tolist(), oStart.tolist(), oEnd.tolist())):
+        if col == 0:
+            val = 1
+        else:
+            fields = bed.fields[i]
+            if len(fields) <= col or fields[col] == "":
+                raise ValueError("track %s: a record has no value in column %d" % (name, col))
+            val = fields[col]
+        val0 = val
+        if useDelta:
+            if prevEnd is not None and s == prevEnd:
+                try:
+                    val0 = float(val) - float(prevVal)
+                except (TypeError, ValueError):
+                    val0 = int(val != prevVal)
+            prevVal, prevEnd = val, e
+            val = 0
+        sym[x] = int(valMap.getMap(val, update=updateValMap))
+        sym0[x] = int(valMap.getMap(val0, update=updateValMap))
+    _check_symbols(sym, name)
+    _check_symbols(sym0, name)
+    return sym0, sym
+
+
+# ---- FASTA ------------------------------------------------------------------------------------------------------------
+def fastaBytes(sequences, chrom, start, end):
+    """bases start .. end of record chrom as T bytes, 0 where there is no base"""
+    out = np.zeros(end - start, dtype=np.uint8)
+    seq = sequences.get(chrom)
+    if seq is not None and start < len(seq):
+        part = np.frombuffer(seq, dtype=np.uint8)[max(start, 0):end]
+        out[:len(part)] = part
+    return out
+
+
+def fastaUpdate(rowBytes, valMap, caseSensitive, updateValMap):
+    """with updateValMap, new symbols in order of first appearance along the row"""
+    if not updateValMap:
+        return
+    b = rowBytes[rowBytes != 0]
+    if not caseSensitive:
+        b = np.frombuffer(b.tobytes().upper(), dtype=np.uint8)
+    uniq, first = np.unique(b, return_index=True)
+    for u in np.argsort(first, kind="stable").tolist():
+        valMap.getMap(chr(int(uniq[u])), update=True)
+
+
+def fastaLut(valMap, caseSensitive, name):
+    """byte -> symbol of a FASTA track as the map stands now (unknown bases: the missing value)"""
+    lut = np.zeros(256, dtype=np.int64)
+    for b in range(1, 256):
+        c = chr(b)
+        lut[b] = int(valMap.getMap(c if caseSensitive else c.upper(), update=False))
+    lut[0] = int(valMap.getMissingVal())
+    _check_symbols(lut, name)
+    return lut.astype(np.uint8)
+
+
+# ---- the device call ---------------------------------------------------------------------------------------------------
+class RecordTrack(object):
+    """one column of a paint: records in row coordinates, sorted by start"""
+    kind = 0
+
+    def __init__(self, fill, start=None, end=None, sym0=None, sym=None):
+        z = np.zeros(0, dtype=np.int64)
+        self.fill = int(fill)
+        self.start = z if start is None else np.asarray(start, dtype=np.int64)
+        self.end = z if end is None else np.asarray(end, dtype=np.int64)
+        self.sym0 = z if sym0 is None else np.asarray(sym0)
+        self.sym = z if sym is None else np.asarray(sym)
+
+
+class SequenceTrack(object):
+    """one column of a paint: T bytes (0 = no base) and their byte -> symbol table"""
+    kind = 1
+
+    def __init__(self, fill, seqBytes, lut):
+        self.fill = int(fill)
+        self.bytes = np.ascontiguousarray(seqBytes, dtype=np.uint8)
+        self.lut = np.ascontiguousarray(lut, dtype=np.uint8)
+
+
+def tileRows():
+    """rows of a tile of the paint kernel"""
+    return int(_lib.load().tehmm_trackio_tile_rows())
+
+
+def paintTracks(T, tracks):
+    """uint8 [T, K] of tehmm_load_tracks_u8 for a list of RecordTrack / SequenceTrack"""
+    T, K = int(T), len(tracks)
+    fill = np.asarray([t.fill for t in tracks], dtype=np.uint8)
+    kind = np.asarray([t.kind for t in tracks], dtype=np.uint8)
+    recs = [t if t.kind == 0 else RecordTrack(0) for t in tracks]
+    seqs = [t for t in tracks if t.kind == 1]
+    ro = np.concatenate([[0], np.cumsum([len(t.start) for t in recs])]).astype(np.int64)
+    so = np.concatenate([[0], np.cumsum([T if t.kind == 1 else 0 for t in tracks])]).astype(np.int64)
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dt)
+    start, end = cat([t.start for t in recs], np.int64), cat([t.end for t in recs], np.int64)
+    sym0, sym = cat([t.sym0 for t in recs], np.uint8), cat([t.sym for t in recs], np.uint8)
+    assert len(start) == len(end) == len(sym0) == len(sym) == ro[-1]
+    for t in seqs:
+        assert t.bytes.shape == (T,) and t.lut.shape == (256,)
+    sb, lut = cat([t.bytes for t in seqs], np.uint8), cat([t.lut for t in seqs], np.uint8)
+    data = np.empty((T, K), dtype=np.uint8)
+    some = lambda a: ptr(a, u8p if a.dtype == np.uint8 else i64p) if len(a) else None
+    _lib.check(_lib.load().tehmm_load_tracks_u8(
+        T, K, ptr(fill, u8p), ptr(kind, u8p), ptr(ro, i64p), some(start), some(end), some(sym0), some(sym),
+        ptr(so, i64p), some(sb), some(lut), ptr(data, u8p) if T else None), "tehmm_load_tracks_u8")
+    return data
+
+
+def lastTiming():
+    """[(pass, milliseconds)] of the device passes of this thread's last tehmm_load_tracks_u8"""
+    names = (ctypes.c_char_p * 16)()
+    ms = (ctypes.c_double * 16)()
+    n = _lib.load().tehmm_trackio_last_timing(16, names, ms)
+    _lib.check(min(n, 0), "tehmm_trackio_last_timing")
+    return [(names[i].decode(), ms[i]) for i in range(n)]
+
+
+# ---- one track over a list of tables -----------------------------------------------------------------------------------
+class TrackSource(object):
+    """A track file read once; columns of any number of tables come from it."""
+
+    def __init__(self, path):
+        if not os.path.isfile(path):
+            raise RuntimeError("Track file not found %s\n" % path)
+        self.path = path
+        ext = os.path.splitext(path)[1]
+        self.bed = self.sequences = None
+        if ext in (".bw", ".bigwig", ".wg", ".bb", ".bigbed"):
+            raise RuntimeError("%s: bigWig / bigBed tracks need bigWigToBedGraph / bigBedToBed, which are not offered; "
+                               "convert the file to BED" % path)
+        if ext == ".bed":
+            self.bed = BedFile(path)
+        elif ext[:3].lower() == ".fa":
+            from .tsd import readFasta
+            self.sequences = readFasta(path)
+        else:
+            sys.stderr.write("Warning: non-BED, non-FASTA file skipped %s\n" % path)
+
+
+class ColumnBuilder(object):
+    """The records (or bytes) of one table column, gathered table after table in the call's row space."""
+
+    def __init__(self, valMap, name):
+        self.valMap, self.name = valMap, name
+        self.parts, self.seq_parts = [], []
+        self.caseSensitive = False
+
+    def add(self, source, offset, chrom, start, end, valCol=None, updateValMap=False, useDelta=False,
+            caseSensitive=False):
+        """the table chrom:start-end lies at rows offset .. offset + end - start; updates the map as the reference"""
+        if source.bed is not None:
+            pick, oStart, oEnd = source.bed.select(chrom, start, end)
+            sym0, sym = recordSymbols(source.bed, pick, oStart, oEnd, chrom, valCol, self.valMap, updateValMap,
+                                      useDelta, self.name)
+            self.parts.append((oStart - start + offset, oEnd - start + offset, sym0, sym))
+        elif source.sequences is not None:
+            row = fastaBytes(source.sequences, chrom, start, end)
+            fastaUpdate(row, self.valMap, caseSensitive, updateValMap)
+            self.caseSensitive = caseSensitive
+            self.seq_parts.append((offset, row))
+
+    def track(self, T):
+        fill = int(self.valMap.getMissingVal())
+        if not 0 <= fill <= MAX_SYMBOL:
+            raise ValueError("track %s: missing value %d does not fit the uint8 table" % (self.name, fill))
+        if self.seq_parts:
+            assert not self.parts
+            b = np.zeros(T, dtype=np.uint8)
+            for offset, row in self.seq_parts:
+                b[offset:offset + len(row)] = row
+            return SequenceTrack(fill, b, fastaLut(self.valMap, self.caseSensitive, self.name))
+        cols = [np.concatenate(c) for c in zip(*self.parts)] or [None] * 4
+        return RecordTrack(fill, *cols)
+
+
+# ---- the reference's functions -----------------------------------------------------------------------------------------
+def _finish(row, outputBuf):
+    if outputBuf is None:
+        return row
+    outputBuf[...] = row
+    return outputBuf
+
+
+def _one(trackPath, chrom, start, end, kwargs, want):
+    valMap = kwargs.get("valMap")
+    if valMap is None:
+        raise ValueError("a value map is required: the rows are bytes")
+    for key in kwargs:
+        if key not in ("valCol", "valMap", "updateValMap", "useDelta", "caseSensitive", "outputBuf"):
+            raise TypeError("unexpected keyword argument %r" % key)
+    source = TrackSource(trackPath)
+    if want == "bed" and source.bed is None or want == "fasta" and source.sequences is None:
+        raise RuntimeError("%s is not a %s file" % (trackPath, want))
+    if source.bed is None and source.sequences is None:
+        return None
+    col = ColumnBuilder(valMap, os.path.basename(trackPath))
+    col.add(source, 0, chrom, int(start), int(end), valCol=kwargs.get("valCol"),
+            updateValMap=bool(kwargs.get("updateValMap", False)), useDelta=bool(kwargs.get("useDelta", False)),
+            caseSensitive=bool(kwargs.get("caseSensitive", False)))
+    T = int(end) - int(start)
+    return _finish(paintTracks(T, [col.track(T)])[:, 0], kwargs.get("outputBuf"))
+
+
+def readBedData(bedPath, chrom, start, end, **kwargs):
+    """One value per base of chrom:start-end from a BED file (trackIO.py:67-212): a uint8 array, or outputBuf filled."""
+    return _one(bedPath, chrom, start, end, kwargs, "bed")
+
+
+def readFastaData(faPath, chrom, start, end, **kwargs):
+    """One value per base of chrom:start-end from a FASTA file (trackIO.py:305-360)."""
+    return _one(faPath, chrom, start, end, kwargs, "fasta")
+
+
+def readTrackData(trackPath, chrom=None, start=None, end=None, **kwargs):
+    """Dispatch on the extension as trackIO.py:23-63: .bed, .fa*; other files are skipped with a warning (None)."""
+    if not os.path.isfile(trackPath):
+        raise RuntimeError("Track file not found %s\n" % trackPath)
+    return _one(trackPath, chrom, start, end, kwargs, None)
