@@ -422,10 +422,24 @@ int tehmm_load_tracks_u8(int64_t T, int K, const uint8_t *fill, const uint8_t *k
                          const int64_t *rec_start, const int64_t *rec_end, const uint8_t *rec_sym0,
                          const uint8_t *rec_sym, const int64_t *seq_offsets, const uint8_t *seq_bytes,
                          const uint8_t *seq_lut, uint8_t *data);
-/* Device time of the passes of the calling thread's last tehmm_load_tracks_u8, as tehmm_segment_last_timing. */
+/* Device time of the passes of the calling thread's last tehmm_load_tracks_u8, tehmm_track_rows_won or
+ * tehmm_load_tracks_f32, as tehmm_segment_last_timing. */
 int tehmm_trackio_last_timing(int max_entries, const char **names, double *milliseconds);
 /* Rows of a tile of the paint kernel (tests cross it). */
 int64_t tehmm_trackio_tile_rows(void);
+
+/* Track scaling (bin/setTrackScaling.py): what the per-base float array of a numeric track holds, from its record
+ * list.  Record tracks only, lists as in tehmm_load_tracks_u8 (row p belongs to the LAST record i of its track with
+ * rec_start[i] <= p < rec_end[i]); there is no first-row value: the tool never takes the delta branch.
+ * tehmm_track_rows_won: won[i] (int64 [rec_offsets[K]]) = rows record i wins, uncovered[k] (int64 [K]) = rows of track
+ * k that no record covers; the won of a track and its uncovered add up to T.
+ * tehmm_load_tracks_f32: out [K][T] (track after track), out[k][p] = rec_val[winner of p] or fill[k].
+ * Both make the checks of tehmm_load_tracks_u8 on T, K and the record lists, before and on the device, with its error
+ * codes and its message about the lowest offending record.  Additions to ABI version 4: detect them by symbol. */
+int tehmm_track_rows_won(int64_t T, int K, const int64_t *rec_offsets, const int64_t *rec_start,
+                         const int64_t *rec_end, int64_t *won, int64_t *uncovered);
+int tehmm_load_tracks_f32(int64_t T, int K, const float *fill, const int64_t *rec_offsets, const int64_t *rec_start,
+                          const int64_t *rec_end, const float *rec_val, float *out);
 
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,

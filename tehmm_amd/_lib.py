@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TEHMM_HIP_LIB") or os.path.join(_HERE, "libtehmm_hip.so")
 
 f64p = ctypes.POINTER(ctypes.c_double)
+f32p = ctypes.POINTER(ctypes.c_float)
 i64p = ctypes.POINTER(ctypes.c_int64)
 i32p = ctypes.POINTER(ctypes.c_int32)
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -75,6 +76,8 @@ SIGNATURES = {
     "tehmm_load_tracks_u8": (c_int, [c_i64, c_int, u8p, u8p, i64p, i64p, i64p, u8p, u8p, i64p, u8p, u8p, u8p]),
     "tehmm_trackio_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_trackio_tile_rows": (c_i64, []),
+    "tehmm_track_rows_won": (c_int, [c_i64, c_int, i64p, i64p, i64p, i64p, i64p]),
+    "tehmm_load_tracks_f32": (c_int, [c_i64, c_int, f32p, i64p, i64p, i64p, f32p, f32p]),
     "tehmm_batch_get_interval_logprobs": (c_int, [vp, f64p]),
     "tehmm_batch_posterior_masksum": (c_int, [vp, f64p, c_i64, c_i64, f64p]),
     "tehmm_batch_map_decode": (c_int, [vp, f64p, f64p]),

@@ -18,6 +18,7 @@
 #include "tehmm_compare.hip.h"
 #include "tehmm_tsd.hip.h"
 #include "tehmm_trackio.hip.h"
+#include "tehmm_scaling.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4127,6 +4128,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
 #include "tehmm_compare_host.inc"
 #include "tehmm_tsd_host.inc"
 #include "tehmm_trackio_host.inc"
+#include "tehmm_scaling_host.inc"
 
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {

@@ -210,6 +210,7 @@ __global__ __launch_bounds__(256) void k_trk_paint(TrkTracks tr, TrkLevels lv, i
         // records [lo, hi) start inside this tile: j, the last record starting at or before a row, lies in [lo - 1, hi)
         const int64_t lo = tr.tile_index[(int64_t)k * (n_tiles + 1) + tile];
         const int64_t hi = tr.tile_index[(int64_t)k * (n_tiles + 1) + tile + 1];
+        // (trk_walk_run of tehmm_scaling.hip.h is a copy of this walk for the kernels there: change the two together)
         int64_t j = -2, w = -1;      // w: the row's winner or -1
 #pragma unroll
         for (int u = 0; u < TEHMM_TRACKIO_RUN; ++u) {

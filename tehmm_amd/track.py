@@ -442,6 +442,47 @@ class Track(object):
     def getPreprocess(self):
         return self.preprocess
 
+    # the setters the scaling tool uses (track.py:202-217); the value map built at construction is not rebuilt, as in
+    # the reference: the attributes take effect in the list read back from the saved XML
+    def setScale(self, scale):
+        self.scale = scale
+        self.logScale = None
+
+    def setLogScale(self, logScale):
+        self.logScale = logScale
+        self.scale = None
+
+    def setShift(self, shift):
+        self.shift = shift
+
+    def toXMLElement(self):
+        """The <track> element of this track (track.py:148-173): logScale wins over scale, false flags are left out."""
+        elem = ET.Element("track")
+        put = lambda key, val: elem.attrib.__setitem__(key, str(val))
+        if self.name is not None:
+            put("name", self.name)
+        if self.path is not None:
+            put("path", self.path)
+        if self.dist is not None:
+            put("distribution", self.dist)
+        if self.valCol is not None:
+            put("valCol", self.valCol)
+        if self.logScale is not None:
+            put("logScale", self.logScale)
+        elif self.scale is not None:
+            put("scale", self.scale)
+        if self.shift is not None:
+            put("shift", self.shift)
+        if self.caseSensitive is not None and self.caseSensitive is not False:
+            put("caseSensitive", self.caseSensitive)
+        if self.delta is True:
+            put("delta", "True")
+        if self.defaultVal is not None:
+            put("default", self.defaultVal)
+        if self.preprocess is not None:
+            put("preprocess", self.preprocess)
+        return elem
+
 
 class TrackList(list):
     """The tracks of a model, by number; mask tracks (track.py:235-346) are kept beside them."""
@@ -469,6 +510,15 @@ class TrackList(list):
         target = self.getMaskTracks() if track.getDist() == "mask" and not treatMaskAsBinary else self
         track.number = len(target)
         target.append(track)
+
+    def saveXML(self, path):
+        """track.py:322-332: the tracks, then the mask tracks, below a teModelConfig root, pretty-printed"""
+        import xml.dom.minidom
+        root = ET.Element("teModelConfig")
+        for track in list(self) + self.getMaskTracks():
+            root.append(track.toXMLElement())
+        with open(path, "w") as f:
+            f.write(xml.dom.minidom.parseString(ET.tostring(root)).toprettyxml())
 
 
 def readTrackList(xmlPath, treatMaskAsBinary=False):

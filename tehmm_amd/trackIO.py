@@ -19,9 +19,14 @@ FASTA tracks: row i is the map of base start + i of record c (upper-cased unless
 the sequence keep the missing value.
 
 Differences from the reference, all deliberate: a line's trailing "\\r\\n" is dropped whole (the reference drops one
-character); a value map is required (rows are bytes); a symbol above 255 raises ValueError naming the track (the
+character); a value map is required for byte rows; a symbol above 255 raises ValueError naming the track (the
 reference's result there depends on the NumPy version); bigWig / bigBed need external tools and raise RuntimeError.
 Not offered: sort= / ignoreBed12= / needIntersect= of readBedData (records are always clipped and sorted here).
+
+Without a value map and with a float32 outputBuf (what bin/setTrackScaling.py of the reference calls; DESIGN.md section
+5p) a BED record's value is np.float32(float(text)), or 1 for valCol 0, and the rows no record covers keep what the
+buffer held.  Text that is no number raises ValueError as in the reference; a value that is not finite raises
+ValueError naming the track (deliberate).  useDelta=True is not offered there.
 """
 import ctypes
 import os
@@ -30,7 +35,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import i64p, ptr, u8p
+from ._lib import f32p, i64p, ptr, u8p
 
 MAX_SYMBOL = 255
 MAX_TRACKS = 128
@@ -292,8 +297,67 @@ def paintTracks(T, tracks):
     return data
 
 
+class FloatTrack(object):
+    """one numeric track: records in row coordinates, sorted by start, a float32 value each"""
+
+    def __init__(self, fill=0.0, start=None, end=None, val=None):
+        z = np.zeros(0, dtype=np.int64)
+        self.fill = np.float32(fill)
+        self.start = z if start is None else np.ascontiguousarray(start, dtype=np.int64)
+        self.end = z if end is None else np.ascontiguousarray(end, dtype=np.int64)
+        self.val = np.zeros(0, dtype=np.float32) if val is None else np.ascontiguousarray(val, dtype=np.float32)
+        assert len(self.start) == len(self.end) == len(self.val)
+
+
+def _record_lists(tracks):
+    ro = np.concatenate([[0], np.cumsum([len(t.start) for t in tracks])]).astype(np.int64)
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dt)
+    return ro, cat([t.start for t in tracks], np.int64), cat([t.end for t in tracks], np.int64), cat
+
+
+def rowsWon(T, tracks):
+    """(rows won by every record: one int64 array per track, uncovered rows: int64 [K]) of tehmm_track_rows_won for a
+    list of tracks with .start / .end"""
+    T, K = int(T), len(tracks)
+    ro, start, end, _ = _record_lists(tracks)
+    won, uncovered = np.zeros(int(ro[-1]), dtype=np.int64), np.zeros(K, dtype=np.int64)
+    some = lambda a: ptr(a, i64p) if len(a) else None
+    _lib.check(_lib.load().tehmm_track_rows_won(T, K, ptr(ro, i64p), some(start), some(end), some(won),
+                                                ptr(uncovered, i64p)), "tehmm_track_rows_won")
+    return [won[ro[k]:ro[k + 1]] for k in range(K)], uncovered
+
+
+def paintTracksFloat(T, tracks):
+    """float32 [K, T] of tehmm_load_tracks_f32 for a list of FloatTrack (one contiguous row array per track)"""
+    T, K = int(T), len(tracks)
+    ro, start, end, cat = _record_lists(tracks)
+    fill, val = np.asarray([t.fill for t in tracks], dtype=np.float32), cat([t.val for t in tracks], np.float32)
+    out = np.empty((K, T), dtype=np.float32)
+    some = lambda a: ptr(a, f32p if a.dtype == np.float32 else i64p) if len(a) else None
+    _lib.check(_lib.load().tehmm_load_tracks_f32(T, K, ptr(fill, f32p), ptr(ro, i64p), some(start), some(end),
+                                                 some(val), ptr(out, f32p) if T else None), "tehmm_load_tracks_f32")
+    return out
+
+
+def recordValues(bed, pick, valCol, name):
+    """float32 value of the selected records without a value map: np.float32(float(text)), 1 for valCol 0"""
+    if valCol is not None and int(valCol) not in (0, 3, 4):
+        raise ValueError("track %s: valCol is 0, 3 or 4" % name)
+    col = 3 if valCol is None else int(valCol)
+    if col == 0 or len(pick) == 0:
+        return np.ones(len(pick), dtype=np.float32)
+    code, values = bed.codes(col)
+    uniq, inv = np.unique(code[pick], return_inverse=True)
+    with np.errstate(over="ignore"):
+        table = np.asarray([np.float32(float(values[int(u)])) for u in uniq], dtype=np.float32)
+    if not np.isfinite(table).all():
+        raise ValueError("track %s: a value that is not finite (%s)" % (name, table[~np.isfinite(table)][0]))
+    return table[inv.reshape(-1)]
+
+
 def lastTiming():
-    """[(pass, milliseconds)] of the device passes of this thread's last tehmm_load_tracks_u8"""
+    """[(pass, milliseconds)] of the device passes of this thread's last tehmm_load_tracks_u8, tehmm_track_rows_won or
+    tehmm_load_tracks_f32"""
     names = (ctypes.c_char_p * 16)()
     ms = (ctypes.c_double * 16)()
     n = _lib.load().tehmm_trackio_last_timing(16, names, ms)
@@ -367,9 +431,27 @@ def _finish(row, outputBuf):
     return outputBuf
 
 
+def _one_float(source, chrom, start, end, kwargs, name):
+    """the float rows of one BED track: painted over what outputBuf holds (NaN marks the rows nothing covers; record
+    values are finite)"""
+    if source.bed is None:
+        raise ValueError("a value map is required: %s is not a BED file" % name)
+    if kwargs.get("useDelta") is True:
+        raise ValueError("track %s: useDelta is not offered without a value map" % name)
+    pick, oStart, oEnd = source.bed.select(chrom, start, end)
+    track = FloatTrack(np.nan, oStart - start, oEnd - start, recordValues(source.bed, pick, kwargs.get("valCol"), name))
+    row = paintTracksFloat(end - start, [track])[0]
+    outputBuf = kwargs["outputBuf"]
+    covered = ~np.isnan(row)
+    outputBuf[covered] = row[covered]
+    return outputBuf
+
+
 def _one(trackPath, chrom, start, end, kwargs, want):
     valMap = kwargs.get("valMap")
-    if valMap is None:
+    outputBuf = kwargs.get("outputBuf")
+    floatRows = valMap is None and outputBuf is not None and outputBuf.dtype == np.float32
+    if valMap is None and not floatRows:
         raise ValueError("a value map is required: the rows are bytes")
     for key in kwargs:
         if key not in ("valCol", "valMap", "updateValMap", "useDelta", "caseSensitive", "outputBuf"):
@@ -379,6 +461,8 @@ def _one(trackPath, chrom, start, end, kwargs, want):
         raise RuntimeError("%s is not a %s file" % (trackPath, want))
     if source.bed is None and source.sequences is None:
         return None
+    if floatRows:
+        return _one_float(source, chrom, int(start), int(end), kwargs, os.path.basename(trackPath))
     col = ColumnBuilder(valMap, os.path.basename(trackPath))
     col.add(source, 0, chrom, int(start), int(end), valCol=kwargs.get("valCol"),
             updateValMap=bool(kwargs.get("updateValMap", False)), useDelta=bool(kwargs.get("useDelta", False)),
