@@ -404,6 +404,54 @@ int tehmm_tsd_last_timing(int max_entries, const char **names, double *milliseco
 /* The longest search window tehmm_tsd_find serves, in bases. */
 int tehmm_tsd_window(void);
 
+/* ---- Mask intervals outside the HMM (cutOutMaskIntervals, bin/interpolateMaskedRegions.py) -------------------------
+ * Interval lists are host columns (int32 chrom id, int64 start, int64 end), uploaded by the call.  The caller numbers
+ * the chroms in the byte-wise order of their names, so that id order is the order of sortBed ("chr10" < "chr2").
+ * A list is SORTED when chrom ids never decrease and, inside a chrom, starts never decrease; DISJOINT when
+ * additionally start[i] >= end[i - 1] inside a chrom.
+ * Every entry point checks before any device call: TEHMM_ERR_ARG for NULL pointers, n < 1, cap < 0;
+ * TEHMM_ERR_UNSUPPORTED for n > 2^31 - 1.  Checked on the device, TEHMM_ERR_ARG with the lowest offending index in
+ * tehmm_last_error: start < end for every interval, and the stated order of each list.
+ * cap / *n_out as in tehmm_tsd_find: on TEHMM_OK *n_out is the number of rows whatever cap is and the first
+ * min(*n_out, cap) rows are written (cap 0: the columns may be NULL); on an error *n_out is 0.
+ * Additions to ABI version 4: detect them by symbol.
+ *
+ * tehmm_intervals_merge: the list is sorted.  A run goes on while start <= the largest end of the run so far
+ * (overlapping AND abutting intervals merge, as mergeBed does by default); the run's interval is written iff
+ * min_len <= end - start <= max_len (filterBedLengths folded in; 0 and INT64_MAX: no filter). */
+int tehmm_intervals_merge(int64_t n, const int32_t *chrom_id, const int64_t *start, const int64_t *end, int64_t min_len,
+                          int64_t max_len, int64_t cap, int32_t *out_chrom, int64_t *out_start, int64_t *out_end,
+                          int64_t *n_out);
+/* A: any intervals in any order, each treated on its own.  B: sorted and disjoint (abutting b are served).
+ * subtract: for every a, in A's order, the maximal parts of a that no b covers, left to right.
+ * intersect: for every a, in A's order, the part a shares with every b that overlaps it, in B's order.
+ * out_src: the index of a.  The cost of the emit pass is bounded by the number of rows written, not by how many b
+ * one a spans: every row is one lane that finds its a in the scanned counts and its piece from the two b beside it. */
+int tehmm_intervals_subtract(int64_t nA, const int32_t *chromA, const int64_t *startA, const int64_t *endA, int64_t nB,
+                             const int32_t *chromB, const int64_t *startB, const int64_t *endB, int64_t cap,
+                             int64_t *out_src, int64_t *out_start, int64_t *out_end, int64_t *n_out);
+int tehmm_intervals_intersect(int64_t nA, const int32_t *chromA, const int64_t *startA, const int64_t *endA, int64_t nB,
+                              const int32_t *chromB, const int64_t *startB, const int64_t *endB, int64_t cap,
+                              int64_t *out_src, int64_t *out_start, int64_t *out_end, int64_t *n_out);
+/* The flank loop of interpolateMaskedRegions.py:117-162.  M: the merged masks, sorted and disjoint.  I: the
+ * prediction, sorted, intervals of equal (chrom, start) by ascending end (the order of the reference's tuple sort);
+ * labels in [0, L) (else TEHMM_ERR_ARG, from the device), L >= 1 (TEHMM_ERR_ARG), L <= 2048 (TEHMM_ERR_UNSUPPORTED).
+ * two_sided / one_sided: uint8 [L] flags; two_sided NULL = every label, one_sided NULL = none.
+ * out_label [nM]: -2 for a mask longer than max_len (not filled), -1 for the default, else a label.  For a mask,
+ * p = the first interval whose (chrom, start, end) is not below the mask's.  The right candidate is I[p], the left
+ * I[p - 1] (none when p = 0).  When no interval is at or above the mask there is NO right candidate and the left
+ * candidate is I[nI - 2] (none when nI = 1): the reference's pointer has stopped on the last index.  A candidate gives
+ * its label when it shares the chrom and abuts (left: end == mask start; right: start == mask end); one that shares
+ * the chrom and overlaps the mask without abutting is the reference's assertion: TEHMM_ERR_ARG naming the lowest such
+ * mask.  The label: only_default -> default; left == right -> left if flagged in two_sided, else default; left
+ * flagged in one_sided -> left; right flagged in one_sided -> right; else default. */
+int tehmm_mask_fill(int64_t nM, const int32_t *chromM, const int64_t *startM, const int64_t *endM, int64_t nI,
+                    const int32_t *chromI, const int64_t *startI, const int64_t *endI, const int32_t *labelI, int L,
+                    const uint8_t *two_sided, const uint8_t *one_sided, int only_default, int64_t max_len,
+                    int32_t *out_label);
+/* Device time of the passes of the calling thread's last call of the four above, as tehmm_segment_last_timing. */
+int tehmm_masking_last_timing(int max_entries, const char **names, double *milliseconds);
+
 /* ---- Track loading (trackIO.readBedData / readFastaData) ---------------------------------------------------------
  * Paints K tracks into data [T, K] (host, row-major, out).  T is the row space of one call: the concatenation of all
  * tables, records already clipped to their table and shifted into it.  fill [K]: the value of a row nothing covers.

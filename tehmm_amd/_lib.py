@@ -73,6 +73,14 @@ SIGNATURES = {
     "tehmm_remove_overlaps": (c_int, [c_i64, i32p, i64p, i64p, c_i64, i64p, i64p, i64p]),
     "tehmm_tsd_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_tsd_window": (c_int, []),
+    "tehmm_intervals_merge": (c_int, [c_i64, i32p, i64p, i64p, c_i64, c_i64, c_i64, i32p, i64p, i64p, i64p]),
+    "tehmm_intervals_subtract": (c_int, [c_i64, i32p, i64p, i64p, c_i64, i32p, i64p, i64p, c_i64, i64p, i64p, i64p,
+                                         i64p]),
+    "tehmm_intervals_intersect": (c_int, [c_i64, i32p, i64p, i64p, c_i64, i32p, i64p, i64p, c_i64, i64p, i64p, i64p,
+                                          i64p]),
+    "tehmm_mask_fill": (c_int, [c_i64, i32p, i64p, i64p, c_i64, i32p, i64p, i64p, i32p, c_int, u8p, u8p, c_int, c_i64,
+                                i32p]),
+    "tehmm_masking_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_load_tracks_u8": (c_int, [c_i64, c_int, u8p, u8p, i64p, i64p, i64p, u8p, u8p, i64p, u8p, u8p, u8p]),
     "tehmm_trackio_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_trackio_tile_rows": (c_i64, []),

@@ -17,8 +17,10 @@ Differences from the reference, all deliberate:
     insertion, as Python 3 does.  The dicts returned by the two comparisons carry their keys in the order in which
     the reference's walk inserts them: the device reports, per cell, where the pair first occurs.
   * summaryRow prints floats as Python 3 does.
-Not offered: --unique, --model (raises in the reference too), --hm, --plot, --window, --tl / --delMask, BED file
-parsing, and a variant that takes a batch's device-resident path.
+--tl / --delMask: cut both lists with masking.cutPair(intervals1, intervals2, tracksXML, delMask) first; that is what
+the two tools do before checkExactOverlap.
+Not offered: --unique, --model (raises in the reference too), --hm, --plot, --window, BED file parsing, and a variant
+that takes a batch's device-resident path.
 """
 import ctypes
 import itertools

@@ -17,6 +17,7 @@
 #include "tehmm_segment.hip.h"
 #include "tehmm_compare.hip.h"
 #include "tehmm_tsd.hip.h"
+#include "tehmm_masking.hip.h"
 #include "tehmm_trackio.hip.h"
 #include "tehmm_scaling.hip.h"
 
@@ -4127,6 +4128,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
 #include "tehmm_segment_host.inc"
 #include "tehmm_compare_host.inc"
 #include "tehmm_tsd_host.inc"
+#include "tehmm_masking_host.inc"
 #include "tehmm_trackio_host.inc"
 #include "tehmm_scaling_host.inc"
 

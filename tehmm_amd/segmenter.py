@@ -9,6 +9,12 @@ all tables go in one call.
     intervals = segmentTracks(trackData, "segments.bed", thresh=1)
     for table in trackData.getTrackTableList():
         table.segment(intervals, trackData.getTrackList())
+
+--delMask K (masks longer than K removed from the region, so that they break contiguity): cut the region before the
+tables are loaded --
+    region = masking.cutOutMaskIntervals(allBed, K, None, tracksXML)      # None: the track list has no mask track
+    trackData.loadTrackData(tracksXML, masking.mergeIntervals(region))
+and call segmentTracks on that trackData.
 """
 import ctypes
 import logging
