@@ -670,20 +670,27 @@ struct BcastOuter<NT, NT> {
 // row broadcast of the previous position's register (the first version read it back from memory: 36 dependent
 // uniform loads per position, 8.6 us per position and wave).  The rows of position t + 1 are requested before
 // position t is worked on.  Small tracks' histograms are privatised in LDS, the others use fp64 global atomics.
-// C, D, start, the histograms are summed into global accumulators with atomics.
+// Reproducible sums: every wave owns one slot of `part` (the layout of the statistics buffer, tehmm_aux.hip.h, slot_cells
+// doubles) and a histogram of its own in LDS, and takes the chunks c = slot, slot + slots, ...: every cell is added to
+// by one lane only, in program order, so the same batch gives the same bits; k_estep_accum_fold adds the slots into
+// the statistics buffer in ascending order.  (Before, the waves added into the shared accumulators in arrival order and
+// two calls differed in the last bits of a quarter of the cells.)
 template <int NT, bool RATIO>
 __global__ __launch_bounds__(256) void k_estep_accum(IntervalTab iv, EmisTab em, int N, int chunk_len,
                                                      const int *chunk_iv, const int64_t *chunk_t0,
                                                      int n_chunks, const double *__restrict__ alpha,
                                                      const double *__restrict__ beta, const double *__restrict__ wrows,
-                                                     const int *__restrict__ escale, double *gC, double *gD,
-                                                     double *gstart, double *gstat) {
+                                                     const int *__restrict__ escale, double *part,
+                                                     int64_t slot_cells) {
   extern __shared__ double sm[];
-  double *lstat = sm;                       // [lds_rows][NT] privatised histogram of the small tracks
-  int *tinfo = (int *)(sm + (size_t)em.lds_rows * NT);     // [3][K]: ldsbase, rowcnt, rowbase (LDS: no per-use scalar loads)
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < em.lds_rows * NT; i += 256) lstat[i] = 0.0;
+  double *lstat = sm + (size_t)w * em.lds_rows * NT;       // [4 waves][lds_rows][NT] privatised histograms of the small tracks
+  int *tinfo = (int *)(sm + (size_t)4 * em.lds_rows * NT); // [3][K]: ldsbase, rowcnt, rowbase (LDS: no per-use scalar loads)
+  // this wave's slot: start[NT] | C[NT][NT] | D[NT] | stat[R + 1][NT] behind the two head cells (stats_off_*)
+  double *slot = part + ((int64_t)blockIdx.x * 4 + w) * slot_cells;
+  double *gstart = slot + 2, *gC = slot + 2 + NT, *gD = slot + 2 + NT + NT * NT, *gstat = slot + 2 + 2 * NT + NT * NT;
+  for (int i = threadIdx.x; i < 4 * em.lds_rows * NT; i += 256) sm[i] = 0.0;
   for (int k = threadIdx.x; k < em.K; k += 256) {
     tinfo[k] = em.ldsbase[k];
     tinfo[em.K + k] = em.rowcnt[k];
@@ -692,8 +699,7 @@ __global__ __launch_bounds__(256) void k_estep_accum(IntervalTab iv, EmisTab em,
   __syncthreads();
   const bool live = lane < N;
   const int jl = min(lane, N - 1);
-  const int c = blockIdx.x * 4 + w;
-  if (c < n_chunks) {
+  for (int c = blockIdx.x * 4 + w; c < n_chunks; c += gridDim.x * 4) {
     const int id = chunk_iv[c];
     const int64_t T = iv.len[id];
     const int64_t p0 = iv.pos0[id];
@@ -778,15 +784,26 @@ __global__ __launch_bounds__(256) void k_estep_accum(IntervalTab iv, EmisTab em,
     }
   }
   __syncthreads();
-  // flush the privatised histogram: LDS row (ldsbase[k] + s) -> global row (rowbase[k] + s)
+  // flush the wave's histogram: LDS row (ldsbase[k] + s) -> row (rowbase[k] + s) of its slot (rows no position of
+  // the wave's chunks added to directly: tracks with lb >= 0 never take the global path)
   for (int k = 0; k < em.K; ++k) {
     const int lb = em.ldsbase[k];
     if (lb < 0) continue;
-    for (int i = threadIdx.x; i < em.rowcnt[k] * NT; i += 256) {
+    for (int i = lane; i < em.rowcnt[k] * NT; i += 64) {
       const double v = lstat[lb * NT + i];
-      if (v != 0.0) atomicAdd(&gstat[(int64_t)em.rowbase[k] * NT + i], v);
+      if (v != 0.0) gstat[(int64_t)em.rowbase[k] * NT + i] += v;
     }
   }
+}
+
+// dst[i] += part[0][i] + part[1][i] + ... in ascending slot order (one thread per cell of the statistics buffer)
+__global__ __launch_bounds__(256) void k_estep_accum_fold(const double *__restrict__ part, int n_slots, int64_t slot_cells,
+                                                          double *dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < 2 || i >= slot_cells) return;         // (cells 0 and 1: the head of the buffer, no statistics)
+  double s = 0.0;
+  for (int k = 0; k < n_slots; ++k) s += part[(int64_t)k * slot_cells + i];
+  dst[i] += s;
 }
 
 // intervals whose forward pass met an impossible row after the first emittable one: the

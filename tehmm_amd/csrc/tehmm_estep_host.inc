@@ -92,17 +92,22 @@ static void launch_estep(const tehmm_model *m, const IntervalTab &iv, const Emis
   constexpr int CPB = NT <= 44 ? 64 : 32;
   const EmisTab emf = n_iv > 256 ? without_lds_tables(em) : em;
   size_t lds = ((size_t)4 * CPB * (NT + 1) + 4 * CPB + 5 * NT + (size_t)emf.lds_rows * NT) * sizeof(double);
-  size_t lds2 = (size_t)std::max(1, m->lds_rows) * NT * sizeof(double) + (size_t)3 * m->K * sizeof(int) + 16;
+  // k_estep_accum: a histogram per wave; w.seq_blocks workgroups share the chunks, every wave with a slot of w.part_seq
+  size_t lds2 = (size_t)4 * std::max(1, m->lds_rows) * NT * sizeof(double) + (size_t)3 * m->K * sizeof(int) + 16;
+  const int64_t ssz = stats_size(NT, m->R);
+  const int gb = std::max(1, std::min(w.seq_blocks, (n_chunks + 3) / 4));
+  (void)hipMemsetAsync(w.part_seq.p, 0, (size_t)gb * 4 * ssz * sizeof(double), st);
   bool_dispatch(ratio, [&](auto r) {
     allow_lds(k_fb_coop<NT, CPB, r>, lds);
     hipLaunchKernelGGL((k_fb_coop<NT, CPB, r>), dim3(n_iv), dim3(256), lds, st, iv, emf, m->N, m->A.p, m->lt.p, m->pi.p,
                        (const double *)(r ? tratios : nullptr), w.alpha.p, w.beta.p, w.fwd_lp.p, w.dead.p, w.wrows.p,
                        w.escale.p);
     allow_lds(k_estep_accum<NT, r>, lds2);
-    hipLaunchKernelGGL((k_estep_accum<NT, r>), dim3((n_chunks + 3) / 4), dim3(256), lds2, st, iv, em, m->N, kEstepChunk,
-                       w.chunk_iv.p, w.chunk_t0.p, n_chunks, w.alpha.p, w.beta.p, w.wrows.p, w.escale.p, w.C, w.D, w.start,
-                       w.stat);
+    hipLaunchKernelGGL((k_estep_accum<NT, r>), dim3(gb), dim3(256), lds2, st, iv, em, m->N, kEstepChunk,
+                       w.chunk_iv.p, w.chunk_t0.p, n_chunks, w.alpha.p, w.beta.p, w.wrows.p, w.escale.p, w.part_seq.p, ssz);
   });
+  hipLaunchKernelGGL(k_estep_accum_fold, dim3((unsigned)((ssz + 255) / 256)), dim3(256), 0, st, (const double *)w.part_seq.p,
+                     gb * 4, ssz, w.stats_base);
 }
 
 static int estep_sequential(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, double *dev_stats, double *lp_out,
@@ -122,10 +127,12 @@ static int estep_sequential(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, doub
     w.rows_cap = 0;
     w.N = N;
   }
-  w.start = dev_stats + stats_off_start();
-  w.C = dev_stats + stats_off_C(NP);
-  w.D = dev_stats + stats_off_D(NP);
-  w.stat = dev_stats + stats_off_stat(NP);
+  w.stats_base = dev_stats;
+  {
+    // per-wave slots of k_estep_accum: one workgroup per CU at most (its LDS holds four histograms), within 1 GB
+    const int64_t slot_bytes = stats_size(NP, m->R) * (int64_t)sizeof(double);
+    w.seq_blocks = (int)std::max<int64_t>(16, std::min<int64_t>(256, ((int64_t)1 << 30) / (4 * slot_bytes)));
+  }
   IntervalTab iv;
   EmisTab em;
   fill_tabs(m, b, iv, em, ratio);     // fit applies the ratios to emissions too (basehmm.py:510)
@@ -173,6 +180,7 @@ static int estep_sequential(tehmm_model_t *m, tehmm_batch_t *b, bool ratio, doub
     giv.order = w.order.p;
     giv.out0 = w.grow0.p;
     const int n_iv = (int)g_order.size(), n_chunks = (int)chunk_iv.size();
+    HIPCHK(w.part_seq.ensure((size_t)std::max(1, std::min(w.seq_blocks, (n_chunks + 3) / 4)) * 4 * (size_t)stats_size(NP, m->R)));
     nt_dispatch(m->NP, [&](auto nt) { launch_estep<nt>(m, giv, em, ratio, n_iv, n_chunks, w, b->ratios.p, b->sP); });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(b->sP));

@@ -313,7 +313,9 @@ struct tehmm_model {
 struct EstepWork {
   DBuf<double> alpha, beta, wrows, fwd_lp;
   DBuf<double> statbuf;            // raw statistics of the host-array entry point (layout: tehmm_aux.hip.h)
-  double *C = nullptr, *D = nullptr, *start = nullptr, *stat = nullptr;   // views into a statistics buffer
+  double *stats_base = nullptr;    // sequential route: the statistics buffer k_estep_accum_fold adds into
+  DBuf<double> part_seq;           // ... and the per-wave slots of k_estep_accum (seq_blocks * 4 of them)
+  int seq_blocks = 0;
   DBuf<int> escale, dead, order, chunk_iv;
   DBuf<int64_t> grow0, chunk_t0;
   int64_t rows_cap = 0;

@@ -39,6 +39,8 @@ def run_case(case, seed0=0, long_mode=False, bign=False, verbose=True):
     big_n = bign and rs.rand() < 0.7      # 64 <= N <= 128
     if big_n:
         N = int(rs.choice([64, 65, 77, 100, 127, 128]))
+    # (1 to 12 tracks, and the draw stays so that a seed keeps making the same case: the branches the track count selects
+    #  from 33 tracks up -- FKW, the 78-track cut-off, the one-hot row table -- are run by tests/test_gpu_track_counts.py)
     K = int(rs.randint(1, 13))
     syms = [int(rs.choice([1, 2, 3, 5, 17, 100, 255])) for _ in range(K)]
     gauss = [k for k in range(K) if syms[k] >= 100 and rs.rand() < 0.5]
