@@ -1323,6 +1323,7 @@ struct EvalKnobs {
   int emis_split;       // TEHMM_EMIS_SPLIT: three-wave emission + gain pass on (1) / off (0); -1: by batch size
   int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
   int gain_window;      // TEHMM_GAIN_WINDOW: positions of an item the gain pass runs on (0: all of them); -1: a quarter
+  bool emis_fast;       // TEHMM_EMIS_FAST=0: the one-wave emission + gain kernel computes its rows with emis_rows everywhere
   bool rowindex_ref;    // TEHMM_ROWINDEX_REF=1 (test-only): index records by k_fused_rowindex_ref, the layout's definition
   // 64 <= N <= 128
   bool wide;            // TEHMM_WIDE=0: the one-wave sequential kernels instead of the four-wave ones (k_*_wide)
@@ -1360,6 +1361,7 @@ static EvalKnobs read_eval_knobs() {
   k.emis_split = std::getenv("TEHMM_EMIS_SPLIT") ? (num("TEHMM_EMIS_SPLIT", 0) != 0 ? 1 : 0) : -1;
   k.defer = num("TEHMM_DEFER", -1);
   k.gain_window = std::getenv("TEHMM_GAIN_WINDOW") ? std::max(0, num("TEHMM_GAIN_WINDOW", 0)) : -1;
+  k.emis_fast = num("TEHMM_EMIS_FAST", 1) != 0;
   k.rowindex_ref = num("TEHMM_ROWINDEX_REF", 0) != 0;
   k.wide = num("TEHMM_WIDE", 1) != 0;
   k.wide_cp = num("TEHMM_WIDE_CP", 1) != 0;
@@ -1828,10 +1830,26 @@ static bool emis_gain_split(int NT, int n_groups, int emis_split) {
   return NT >= 12 && (emis_split >= 0 ? emis_split != 0 : n_groups < 2048);
 }
 
-// emission rows (fp64 log rows for the exact Viterbi pass) and P0 in one pass
+// Whether the one-wave emission + gain kernel may compute its rows in the fast form (tehmm_emis_fast.hip.h): no ratios of
+// either kind, normalize 1.0, at most 12 tracks, every LDS-staged track ahead of every global-table track, pads among the
+// last three entries of a row only, a warm-up of whole observation blocks, table offsets that fit 32 bits.
+static bool emis_fast_ok(const tehmm_model *m, const EmisTab &em, int Wu, bool ratio) {
+  if (ratio || em.ratios || em.normalize != 1.0 || em.K > 12 || em.KPW > 3) return false;
+  if (m->NP > TEHMM_EFAST_NT_MAX || m->N < m->NP - 3 || Wu % TEHMM_EFAST_PB != 0) return false;
+  if (((int64_t)em.zero_row + 1) * m->NP * 8 >= ((int64_t)1 << 31)) return false;
+  bool glb = false;
+  for (int k = 0; k < em.K; ++k) {
+    if (em.ldsbase[k] < 0) glb = true;
+    else if (glb) return false;
+  }
+  return true;
+}
+
+// emission rows (fp64 log rows for the exact Viterbi pass) and P0 in one pass; fast: emis_fast_ok and the knob allow the
+// fast form of the one-wave kernel's rows (EvalPlan::emis_fast)
 template <int NT>
 static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em,
-                                  int CS, int Wu, int Wn, bool ratio, int emis_split, hipStream_t st) {
+                                  int CS, int Wu, int Wn, bool ratio, int emis_split, bool fast, hipStream_t st) {
   LaneWork &lw = b->lw;
   // round 4: the states of a row split over the three waves of a unit (tehmm_lane3.hip.h); TEHMM_EMIS_SPLIT=0 keeps
   // the one-wave kernel (which also serves the smallest models); emis_split: that knob, -1 if not set
@@ -1861,6 +1879,22 @@ static void launch_emis_gain_lane(tehmm_batch *b, const tehmm_model *m, const In
     hipLaunchKernelGGL((k_emis_gain_lane<NT, true>), dim3((lw.n_groups + 3) / 4), dim3(256), lds, st, iv, em,
                        lane_geom(lw), m->N, CS, Wu, 0, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
                        (const double *)b->ratios.p);
+    return;
+  }
+  if constexpr (NT <= TEHMM_EFAST_NT_MAX) if (fast) {
+    // (behind the table: the observation blocks of the four waves)
+    const size_t ldsf = lds + 4 * (size_t)TEHMM_EFAST_WAVE_BYTES;
+    if (Wn > 0) {
+      allow_lds(k_emis_gain_lane<NT, false, true, true>, ldsf);
+      hipLaunchKernelGGL((k_emis_gain_lane<NT, false, true, true>), dim3((lw.n_groups + 3) / 4), dim3(256), ldsf, st, iv, em,
+                         lane_geom(lw), m->N, CS, Wu, Wn, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
+                         (const double *)nullptr);
+    } else {
+      allow_lds(k_emis_gain_lane<NT, false, false, true>, ldsf);
+      hipLaunchKernelGGL((k_emis_gain_lane<NT, false, false, true>), dim3((lw.n_groups + 3) / 4), dim3(256), ldsf, st, iv, em,
+                         lane_geom(lw), m->N, CS, Wu, 0, (const float *)m->ltP.p, lw.B.p, lw.vgain.p,
+                         (const double *)nullptr);
+    }
     return;
   }
   if (Wn > 0) {
@@ -2809,6 +2843,8 @@ struct EvalPlan {
   // ahead of the placement and the one-wave emission kernel runs: split_post, device placement, no segment ratios,
   // items of at least 128 positions.  Knob, else a quarter of the item (a multiple of 32).
   int gain_window;
+  // The one-wave emission + gain kernel computes its rows in the fast form (emis_fast_ok; knob: emis_rows everywhere).
+  bool emis_fast;
   // Order of the posterior against the Viterbi pipeline (knob, else by size): 0 none; 1 behind the Viterbi passes;
   // 3 (fused lane passes) the forward half from the start, beside the emission-row kernel and the binade placement,
   // the quantised pass behind the forward pass, the backward half behind it, next to the exact chain.
@@ -2886,6 +2922,12 @@ static void plan_gain_window(EvalPlan &p, const tehmm_model *m, const tehmm_batc
   if (wn > 0 && wn + p.WuV <= p.LS) p.gain_window = wn;
 }
 
+// EvalPlan::emis_fast, behind lane_prepare for the same reason
+static void plan_emis_fast(EvalPlan &p, const tehmm_model *m, const tehmm_batch *b, const EmisTab &em, const EvalKnobs &kn) {
+  p.emis_fast = kn.emis_fast && (p.vlane || p.glane) && p.emis_gain &&
+                !emis_gain_split(m->NP, b->lw.n_groups, kn.emis_split) && emis_fast_ok(m, em, p.WuV, p.ratio);
+}
+
 // What the stages of one call share.
 struct EvalCtx {
   tehmm_model *m;
@@ -2937,7 +2979,7 @@ static int eval_emis_p0(EvalCtx &c) {
     // emission rows of every position, once, item-interleaved (log rows for Viterbi, linear for fwd/bwd)
     if (p.emis_gain) {
       nt_dispatch(m->NP, [&](auto nt) {
-        launch_emis_gain_lane<nt>(b, m, c.iv, c.em, p.CS, p.WuV, p.gain_window, p.ratio, c.kn.emis_split, st);
+        launch_emis_gain_lane<nt>(b, m, c.iv, c.em, p.CS, p.WuV, p.gain_window, p.ratio, c.kn.emis_split, p.emis_fast, st);
       });
     } else {
       nt_dispatch(m->NP, [&](auto nt) {
@@ -3402,6 +3444,7 @@ static int eval_counters(const EvalCtx &c) {
     add("count:viterbi_exact_blocks", st[0]);
     add("count:viterbi_chunk_jumps", st[1]);
     add("count:gain_window", c.p.gain_window);
+    add("count:emis_fast", c.p.emis_fast ? 1 : 0);
   }
   return TEHMM_OK;
 }
@@ -3446,6 +3489,7 @@ int tehmm_eval_batch(tehmm_model_t *m, tehmm_batch_t *b, int flags, double *vite
     rc = lane_prepare(b, m, p.CS, p.LS, p.flane, p.vlane, p.glane, p.fused_fb, !p.emis_gain);
     if (rc) return rc;
     plan_gain_window(p, m, b, kn);
+    plan_emis_fast(p, m, b, c.em, kn);
   }
   if (p.flane) {
     rc = fb_warmup(b, m, p.LS, c.iv, c.emg, kn, &c.WuF);

@@ -19,6 +19,7 @@
 //     into the [T][N] posterior with an LDS transpose.
 #pragma once
 #include "tehmm_spec.hip.h"
+#include "tehmm_emis_fast.hip.h"
 
 namespace tehmm {
 
@@ -1176,7 +1177,10 @@ __global__ __launch_bounds__(256) void k_vit_gain_lane(IntervalTab iv, LaneGeom 
 // completes it with the forward pass's log-scale records (tehmm_place.hip.h: place_item_gain).  P0 is 55 % of this
 // kernel's vector instructions and no result depends on it.  Rows, NaN marking and the NaN gain are the full pass's.
 // ------------------------------------------------------------------------------------------
-template <int NT, bool RATIO = false, bool WIN = false>
+// FAST: the row part in its fast form (tehmm_emis_fast.hip.h; host: emis_fast_ok) -- observation rows staged through
+// the wave's LDS area behind the table, track metadata in registers, pads masked among the last three entries only, the
+// NaN row store on a wave-uniform branch.  Same rows, same marking, same gains.
+template <int NT, bool RATIO = false, bool WIN = false, bool FAST = false>
 #ifndef TEHMM_EMIS_WAVES
 #define TEHMM_EMIS_WAVES 2
 #endif
@@ -1217,19 +1221,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TEHMM_EMIS_
     return mx;
   };
   float g0 = 0.f;
+  ObsWindow ow;
+  EmisFastRows<NT> fr;
+  if (FAST) {
+    fr.init(em, emis_ltab, lane);
+    ow.src = em.obs32 + (p0 + t0) * em.KPW;
+    ow.stage = (unsigned)(size_t)(__attribute__((address_space(3))) const double *)emis_ltab +
+               (unsigned)(em.lds_rows * NT * 8) + (threadIdx.x >> 6) * TEHMM_EFAST_WAVE_BYTES + lane * 4;
+    ow.KPW = em.KPW;
+    ow.s0 = s_first;
+    ow.lo = run ? s_first : 0;
+    ow.hi = len;
+    ow.request(0);                                          // (block b + 1 is on its way while block b is read)
+    ow.commit();
+    ow.request(1);
+  }
   for (int s = s_first; s < maxlen; ++s) {
     const bool act = s >= 0 ? s < len : run;
     const int64_t gpos = p0 + t0 + (act ? s : 0);
     double x[NT];
-    emis_rows<NT>(em, emis_ltab, gpos, x);
-    double m = x[0];
+    bool good;
+    if (FAST) {
+      const int rel = (s - s_first) & (TEHMM_EFAST_PB - 1);
+      ow.words(rel, fr.w0, fr.w1, fr.w2);
+      fr.rows(x);
+      // (wave-uniform) behind the block's last position its successor goes to LDS and the one after that is requested:
+      // here, behind the wait for the last table gather and ahead of the row stores, the wait for it costs nothing
+      if (rel == TEHMM_EFAST_PB - 1) {
+        ow.commit();
+        ow.request((s - s_first) / TEHMM_EFAST_PB + 2);
+      }
+      double m = x[0];
 #pragma unroll
-    for (int j = 1; j < NT; ++j) m = fmax(m, j < N ? x[j] : -INFINITY);
-    const bool good = m > -1e20;
-    if (B && s >= 0 && act) {
-      const int64_t o = ((((int64_t)g * lg.L + s) * NT) << 6) + lane;
+      for (int j = 1; j < NT; ++j) m = fmax(m, (j < NT - 3 || j < N) ? x[j] : -INFINITY);     // (host: N >= NT - 3)
+      good = m > -1e20;
+      if (__any(!good)) {
+        if (B && s >= 0 && act) {
+          const int64_t o = ((((int64_t)g * lg.L + s) * NT) << 6) + lane;
+          double q = qnan;
+          asm volatile("" : "+v"(q));                       // (keeps the selects on this side of the branch)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) B[o + ((int64_t)j << 6)] = good ? x[j] : qnan;
+          for (int j = 0; j < NT; ++j) B[o + ((int64_t)j << 6)] = good ? x[j] : q;
+        }
+      } else if (B && s >= 0 && act) {
+        const int64_t o = ((((int64_t)g * lg.L + s) * NT) << 6) + lane;
+#pragma unroll
+        // (non-temporal: the rows are read back, once, after more data than the caches hold has gone by -- 8.93 -> 8.52 ms alone)
+        for (int j = 0; j < NT; ++j) __builtin_nontemporal_store(x[j], &B[o + ((int64_t)j << 6)]);
+      }
+    } else {
+      emis_rows<NT>(em, emis_ltab, gpos, x);
+      double m = x[0];
+#pragma unroll
+      for (int j = 1; j < NT; ++j) m = fmax(m, j < N ? x[j] : -INFINITY);
+      good = m > -1e20;
+      if (B && s >= 0 && act) {
+        const int64_t o = ((((int64_t)g * lg.L + s) * NT) << 6) + lane;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) B[o + ((int64_t)j << 6)] = good ? x[j] : qnan;
+      }
     }
     bad = bad | (act && !good);
     if (WIN && s < s_p0) continue;                        // (wave-uniform: W still holds its zeros at s_p0)
