@@ -265,6 +265,32 @@ int tehmm_model_mstep(tehmm_model_t *model, const double *dev_stats, int update_
  * the cells of real symbols are written); any pointer may be NULL. */
 int tehmm_model_get_params(tehmm_model_t *model, double *log_transmat, double *log_startprob, double *logProbs);
 
+/* ---- semi-supervised Baum-Welch: user constraints on the model handle (detected by symbol) --------
+ * The reference re-applies its --forceTransProbs / --forceEmProbs / --forceStartProbs files after every M-step
+ * (hmm.py:608-614).  Here the files become tables that live on the handle: uploaded once by this call and applied by
+ * every later tehmm_model_mstep -- after its update kernels, before the derived layouts are rebuilt, in the
+ * reference's order (transitions, emissions, start) and whatever the update_* flags say.
+ *   trans_mask / trans_val [N][N], start_mask / start_val [N]: mask != 0 forces the cell to the probability in val;
+ *     the other cells of the row (of the vector) are scaled to the mass that leaves, or zeroed when none is left
+ *     (applyUserTrans, hmm.py:357-429; applyUserStarts, hmm.py:432-488);
+ *   emis_mask / emis_val [K][N][S]: mask bit 0 forces the cell; bit 1, set on EVERY cell of a gaussian track, keeps
+ *     the track's rows out of the rescale (a forced gaussian row is a whole row, filled by the caller from its
+ *     (mu, sigma)).  Per (track, state) the unforced symbols are scaled, or -- when their mass is zero and the forced
+ *     ones total less than 1 -- the leftover is added to them (applyUserEmissions, emission.py:347-438); then every
+ *     real-symbol cell of every track goes through log(exp(x)) with zeros at -1e100, as the reference's closing myLog;
+ *   trans_epsilons: the model's transMatEpsilons -- whenever a transition matrix with an exact zero is written (by the
+ *     M-step's update or by the forced cells) machine epsilon is added to all its cells first (hmm.py:629-645: the
+ *     setter drops the result of normalize(axis=1), so only that function's in-place `+= eps` takes effect).
+ * Any pair may be NULL; all NULL with trans_epsilons = 0 clears the constraints.  Checked here, TEHMM_ERR_ARG: a mask
+ * without its values, forced mass above 1, a (track, state) with every symbol forced to less than 1 in total.
+ * TEHMM_ERR_UNSUPPORTED for N > 128.  What only the device can see (nothing learned left to scale under forced zeros:
+ * the reference's assertion; a value that is not finite) makes the M-step return TEHMM_ERR_ARG, with the handle's
+ * parameters those from before that call.  A constrained M-step adds no synchronisation and no upload to a plain
+ * one, and copies one status word back.  None of this has been timed. */
+int tehmm_model_set_constraints(tehmm_model_t *model, const uint8_t *trans_mask, const double *trans_val,
+                                const uint8_t *start_mask, const double *start_val, const uint8_t *emis_mask,
+                                const double *emis_val, int trans_epsilons);
+
 /* ---- the step before the path: segment compression and mask compaction --------
  * TrackTable.segment = interpolateSegments + compressSegments (track.py:449-533, 594-620) for a uint8
  * table data [T][K] and ascending table-relative segOffsets [n_seg]: out [n_seg][K] holds the mode of

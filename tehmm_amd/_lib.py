@@ -51,6 +51,7 @@ SIGNATURES = {
     "tehmm_model_mstep": (c_int, [vp, vp, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, i32p, f64p, c_dbl,
                                   f64p]),
     "tehmm_model_get_params": (c_int, [vp, f64p, f64p, f64p]),
+    "tehmm_model_set_constraints": (c_int, [vp, u8p, f64p, u8p, f64p, u8p, f64p, c_int]),
     "tehmm_segment_table_u8": (c_int, [c_i64, c_int, u8p, c_i64, i64p, u8p, f64p, u8p, f64p]),
     "tehmm_mask_table_u8": (c_int, [c_i64, c_int, u8p, c_int, u8p, u8p, i32p, u8p, i32p, i64p]),
     "tehmm_segment_offsets_u8": (c_int, [c_int, i64p, c_int, u8p, u8p, u8p, c_int, c_int, c_i64, c_i64, c_i64, i64p,

@@ -183,8 +183,20 @@ __device__ __forceinline__ double my_log(double x, double log_zero) {      // co
 }
 
 // transitions + start: one thread per state (row).  lt [NP][NP] in / out, pi [NP] in / out.
+// eps_norm (transMatEpsilons, the transmat_ setter of hmm.py:629-645): when any cell of the new matrix is exactly zero,
+// machine epsilon is added to every cell of the matrix, the orphaned rows it keeps included.  (The setter calls
+// normalize(axis=1) and drops what it returns: only the in-place `+= eps` of that function takes effect, the rows
+// are not divided by their sums -- quirk Q24.)
+__device__ __forceinline__ double mstep_trans_cell(const double *lt, const double *C, const double *D, int i, int j,
+                                                   int NP, double invN, double trans_prior, double rowsum, bool keep) {
+  if (keep) return exp(lt[i * NP + j]);
+  double v = exp(lt[i * NP + j]) * C[i * NP + j];
+  if (i == j) v += D[i];
+  return (trans_prior - 1.0 + v * invN) / rowsum;
+}
+
 __global__ void k_mstep_trans(int N, int NP, const double *stats, int do_start, int do_trans,
-                              double start_prior, double trans_prior, double *lt, double *pi) {
+                              double start_prior, double trans_prior, double *lt, double *pi, int eps_norm) {
   const int i = threadIdx.x;
   __shared__ double sh[128];
   if (do_start) {
@@ -198,7 +210,31 @@ __global__ void k_mstep_trans(int N, int NP, const double *stats, int do_start, 
     if (i < N) pi[i] = my_log(v / tot, -1e100);
     __syncthreads();
   }
-  if (do_trans && i < N) {
+  if (do_trans && eps_norm) {                    // (block-uniform: every thread meets the barrier below)
+    const double *C = stats + stats_off_C(NP), *D = stats + stats_off_D(NP);
+    const double invN = 1.0 / (double)N;
+    double rowsum = 0.0;
+    bool keep = false;
+    int zero = 0;
+    if (i < N) {
+      for (int j = 0; j < N; ++j) {
+        double v = exp(lt[i * NP + j]) * C[i * NP + j];
+        if (i == j) v += D[i];
+        rowsum += trans_prior - 1.0 + v * invN;
+      }
+      keep = rowsum < TEHMM_DBL_EPS;
+      for (int j = 0; j < N; ++j)
+        zero |= mstep_trans_cell(lt, C, D, i, j, NP, invN, trans_prior, rowsum, keep) == 0.0;
+    }
+    const int any_zero = __syncthreads_or(zero);
+    if (i < N && (any_zero || !keep)) {
+      // (each cell is read before it is written and no later cell reads it: in place is safe)
+      for (int j = 0; j < N; ++j) {
+        const double v = mstep_trans_cell(lt, C, D, i, j, NP, invN, trans_prior, rowsum, keep);
+        lt[i * NP + j] = my_log(any_zero ? v + TEHMM_DBL_EPS : v, -1e100);
+      }
+    }
+  } else if (do_trans && i < N) {
     const double *C = stats + stats_off_C(NP), *D = stats + stats_off_D(NP);
     const double invN = 1.0 / (double)N;
     double rowsum = 0.0;
@@ -279,6 +315,113 @@ __global__ void k_mstep_gauss(MstepTracks tr, int n_gauss, const int *gtracks, c
   }
   for (int s = 1; s < cnt; ++s)
     tab[(int64_t)(rb + s) * NP + j] = my_log(exp(tab[(int64_t)(rb + s) * NP + j]) / tot, -1e100);
+}
+
+// ------------------------------------------------------------------------------------------
+// User constraints, re-applied after every M-step (MultitrackHmm.applyUserTrans / applyUserStarts, hmm.py:357-488;
+// emission.applyUserEmissions, emission.py:347-438).  Masks and values in the caller's shapes: trans [N][N],
+// start [N], emission [K][N][S]; values are probabilities.  What only the device can see -- a learned mass of zero
+// where the reference asserts, a result that is not finite -- raises bits in *status (never lowered here).
+// ------------------------------------------------------------------------------------------
+#define TEHMM_CSTAT_EMIS_ZERO 1      // emissions: nothing learned left to scale and the forced symbols total zero
+#define TEHMM_CSTAT_NONFINITE 2      // a constrained transition / start / emission value is inf or nan
+
+__device__ __forceinline__ double constrained_cell(bool forced, double val, double cur_p, double tgt, double cur) {
+  if (forced) return val;
+  return tgt == 0.0 ? 0.0 : cur_p * (tgt / cur);
+}
+
+// transitions and start: one workgroup of 128, one thread per row (transitions) / per state (start).  tmask / smask may
+// be NULL.  trans_eps: the setter's `+= eps` (see k_mstep_trans) when any cell of the constrained matrix is zero.
+__global__ void k_constrain_trans(int N, int NP, const uint8_t *tmask, const double *tval, const uint8_t *smask,
+                                  const double *sval, int trans_eps, double *lt, double *pi, int *status) {
+  const int i = threadIdx.x;
+  int bad = 0;
+  if (tmask) {                                   // (block-uniform)
+    double cur = 0.0, tgt = 1.0;
+    int zero = 0;
+    if (i < N) {
+      for (int j = 0; j < N; ++j) {
+        if (tmask[i * N + j]) tgt -= tval[i * N + j];
+        else cur += exp(lt[i * NP + j]);
+      }
+      for (int j = 0; j < N; ++j) {
+        const double p = constrained_cell(tmask[i * N + j] != 0, tval[i * N + j], exp(lt[i * NP + j]), tgt, cur);
+        zero |= p == 0.0;
+        bad |= !isfinite(p);
+      }
+    }
+    const int any_zero = trans_eps ? __syncthreads_or(zero) : 0;
+    if (i < N) {
+      for (int j = 0; j < N; ++j) {
+        const double p = constrained_cell(tmask[i * N + j] != 0, tval[i * N + j], exp(lt[i * NP + j]), tgt, cur);
+        lt[i * NP + j] = my_log(any_zero ? p + TEHMM_DBL_EPS : p, -1e100);
+      }
+    }
+  }
+  if (smask) {                                   // (block-uniform)
+    double p = 0.0;
+    if (i < N) {
+      double cur = 0.0, tgt = 1.0;
+      for (int j = 0; j < N; ++j) {
+        if (smask[j]) tgt -= sval[j];
+        else cur += exp(pi[j]);
+      }
+      p = constrained_cell(smask[i] != 0, sval[i], exp(pi[i]), tgt, cur);
+      bad |= !isfinite(p);
+    }
+    __syncthreads();                             // every state has read the old vector
+    if (i < N) pi[i] = my_log(p, -1e100);
+  }
+  if (bad) atomicOr(status, TEHMM_CSTAT_NONFINITE);
+}
+
+// emissions: one thread per (track, state), as k_mstep_emis.  Mask bit 0: the cell is forced to its value; bit 1 (set on
+// every cell of a gaussian track): the row takes no part in the rescale -- its forced cells (a whole row, filled by
+// the host's applyGaussian) are restored, the others stay.  Every real-symbol cell then goes through
+// my_log(exp(x), -1e100), named in the user file or not: the -1e6 of k_mstep_emis becomes -1e100 (emission.py:436).
+__global__ void k_constrain_emis(MstepTracks tr, int N, int NP, int S, const uint8_t *emask, const double *evals,
+                                 double *tab, int *status) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= tr.K * N) return;
+  const int k = idx / N, j = idx - k * N;
+  const int rb = tr.rowbase[k], cnt = tr.rowcnt[k];
+  if (cnt < 2) return;
+  const uint8_t *mk = emask + ((int64_t)k * N + j) * S;
+  const double *vl = evals + ((int64_t)k * N + j) * S;
+  int bad = 0;
+  if (mk[1] & 2) {
+    for (int s = 1; s < cnt; ++s) {
+      double *cell = tab + (int64_t)(rb + s) * NP + j;
+      *cell = my_log((mk[s] & 1) ? vl[s] : exp(*cell), -1e100);
+    }
+    return;
+  }
+  double cur = 0.0, tgt = 1.0;
+  int forced = 0;
+  for (int s = 1; s < cnt; ++s) {
+    if (mk[s] & 1) { tgt -= vl[s]; ++forced; }
+    else cur += exp(tab[(int64_t)(rb + s) * NP + j]);
+  }
+  // forced symbols that total less than 1 with nothing learned to scale: the leftover is ADDED (emission.py:401-420)
+  const bool additive = cur == 0.0 && tgt < 1.0;
+  double amt;
+  if (additive) {
+    amt = (1.0 - tgt) / (double)(cnt - 1 - forced);       // (no unforced symbol: refused when the tables were set)
+  } else {
+    if (!(cur > 0.0)) bad |= TEHMM_CSTAT_EMIS_ZERO;       // the reference's `assert curTotal > 0.`
+    amt = tgt / cur;
+  }
+  for (int s = 1; s < cnt; ++s) {
+    double *cell = tab + (int64_t)(rb + s) * NP + j;
+    double p;
+    if (mk[s] & 1) p = vl[s];
+    else if (tgt == 0.0) p = 0.0;
+    else p = additive ? exp(*cell) + amt : exp(*cell) * amt;
+    if (!isfinite(p)) bad |= TEHMM_CSTAT_NONFINITE;
+    *cell = my_log(p, -1e100);
+  }
+  if (bad) atomicOr(status, bad);
 }
 
 // every other layout of the transition table from lt [NP][NP] (pads -inf): transposes, linear copies,

@@ -112,6 +112,31 @@ static MstepTracks mstep_tracks(const tehmm_model *m) {
   return tr;
 }
 
+// every copy derived from tab (emission) / lt (trans) that the M-step or a constraint rewrote
+static int mstep_rebuild(tehmm_model *m, const MstepTracks &tr, bool emission, bool trans) {
+  const int N = m->N, NP = m->NP;
+  if (emission) {
+    if (int rcp = build_ptab(m)) return rcp;
+    if (m->lds_rows > 0) {
+      DBuf<int> d_lb;
+      HIPCHK(d_lb.upload(m->ldsbase, (size_t)m->K));
+      hipLaunchKernelGGL(k_model_ltab, dim3(m->K), dim3(256), 0, 0, tr, (const int *)d_lb.p, NP,
+                         (const double *)m->tab.p, m->ltab.p);
+      HIPCHK(hipDeviceSynchronize());
+    }
+  }
+  if (trans) {
+    hipLaunchKernelGGL(k_model_layouts, dim3(grid_for((int64_t)NP * NP, 256)), dim3(256), 0, 0, NP,
+                       (const double *)m->lt.p, m->ltT.p, m->A.p, m->AT.p, m->ltG.p, m->AG.p, m->ATG.p, m->ltP.p);
+    // host copy of the log-transition matrix (binade tables of the exact Viterbi, E-step transform)
+    std::vector<double> hlt((size_t)NP * NP);
+    HIPCHK(hipMemcpy(hlt.data(), m->lt.p, hlt.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) m->h_lt[(size_t)i * N + j] = hlt[(size_t)i * NP + j];
+  }
+  return TEHMM_OK;
+}
+
 int tehmm_model_mstep(tehmm_model_t *m, const double *dev_stats, int update_start, int update_trans,
                       int update_emission, double startprob_prior, double transmat_prior, double fudge,
                       int n_gauss, const int32_t *gauss_tracks, const double *gauss_values, double uniform_mix,
@@ -124,9 +149,21 @@ int tehmm_model_mstep(tehmm_model_t *m, const double *dev_stats, int update_star
       return fail(TEHMM_ERR_ARG, "tehmm_model_mstep: gaussian track index out of range");
   const int N = m->N, NP = m->NP;
   const MstepTracks tr = mstep_tracks(m);
+  const size_t n_tab = (size_t)(m->R + 1) * NP;
+  // (transMatEpsilons alone launches no constraint kernel: nothing can raise the status word, nothing to put back)
+  const bool forced = m->c_trans || m->c_start || m->c_emis;
+  if (forced) {
+    // what a failed constraint puts back (device to device, in stream order: no synchronisation)
+    HIPCHK(hipMemcpyAsync(m->c_save.p, m->lt.p, (size_t)NP * NP * sizeof(double), hipMemcpyDeviceToDevice, 0));
+    HIPCHK(hipMemcpyAsync(m->c_save.p + (size_t)NP * NP, m->pi.p, (size_t)NP * sizeof(double),
+                          hipMemcpyDeviceToDevice, 0));
+    HIPCHK(hipMemcpyAsync(m->c_save.p + (size_t)NP * NP + NP, m->tab.p, n_tab * sizeof(double),
+                          hipMemcpyDeviceToDevice, 0));
+    HIPCHK(hipMemsetAsync(m->c_status.p, 0, sizeof(int), 0));
+  }
   if (update_start || update_trans)
     hipLaunchKernelGGL(k_mstep_trans, dim3(1), dim3(128), 0, 0, N, NP, dev_stats, update_start, update_trans,
-                       startprob_prior, transmat_prior, m->lt.p, m->pi.p);
+                       startprob_prior, transmat_prior, m->lt.p, m->pi.p, m->c_eps ? 1 : 0);
   if (update_emission) {
     hipLaunchKernelGGL(k_mstep_emis, dim3(grid_for((int64_t)m->K * N, 64)), dim3(64), 0, 0, tr, N, NP, dev_stats,
                        fudge, m->tab.p);
@@ -144,27 +181,112 @@ int tehmm_model_mstep(tehmm_model_t *m, const double *dev_stats, int update_star
       else
         HIPCHK(hipDeviceSynchronize());
     }
-    if (int rcp = build_ptab(m)) return rcp;
-    if (m->lds_rows > 0) {
-      DBuf<int> d_lb;
-      HIPCHK(d_lb.upload(m->ldsbase, (size_t)m->K));
-      hipLaunchKernelGGL(k_model_ltab, dim3(m->K), dim3(256), 0, 0, tr, (const int *)d_lb.p, NP,
-                         (const double *)m->tab.p, m->ltab.p);
-      HIPCHK(hipDeviceSynchronize());
-    }
   }
-  if (update_trans) {
-    hipLaunchKernelGGL(k_model_layouts, dim3(grid_for((int64_t)NP * NP, 256)), dim3(256), 0, 0, NP,
-                       (const double *)m->lt.p, m->ltT.p, m->A.p, m->AT.p, m->ltG.p, m->AG.p, m->ATG.p, m->ltP.p);
-    // host copy of the log-transition matrix (binade tables of the exact Viterbi, E-step transform)
-    std::vector<double> hlt((size_t)NP * NP);
-    HIPCHK(hipMemcpy(hlt.data(), m->lt.p, hlt.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < N; ++i)
-      for (int j = 0; j < N; ++j) m->h_lt[(size_t)i * N + j] = hlt[(size_t)i * NP + j];
-  }
+  // the user constraints, in the reference's order (hmm.py:608-614: transitions, emissions, start), whatever the
+  // update flags say; transMatEpsilons alone belongs to the transition update (k_mstep_trans)
+  if (m->c_trans || m->c_start)
+    hipLaunchKernelGGL(k_constrain_trans, dim3(1), dim3(128), 0, 0, N, NP, (const uint8_t *)m->c_tmask.p,
+                       (const double *)m->c_tval.p, (const uint8_t *)m->c_smask.p, (const double *)m->c_sval.p,
+                       m->c_eps ? 1 : 0, m->lt.p, m->pi.p, m->c_status.p);
+  if (m->c_emis)
+    hipLaunchKernelGGL(k_constrain_emis, dim3(grid_for((int64_t)m->K * N, 64)), dim3(64), 0, 0, tr, N, NP, m->S,
+                       (const uint8_t *)m->c_emask.p, (const double *)m->c_eval.p, m->tab.p, m->c_status.p);
+  if (int rc = mstep_rebuild(m, tr, update_emission || m->c_emis, update_trans || m->c_trans)) return rc;
   HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
+  if (forced) {
+    // the status word comes with the synchronisation every M-step ends in
+    int status = 0;
+    HIPCHK(hipMemcpy(&status, m->c_status.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (status != 0) {
+      HIPCHK(hipMemcpy(m->lt.p, m->c_save.p, (size_t)NP * NP * sizeof(double), hipMemcpyDeviceToDevice));
+      HIPCHK(hipMemcpy(m->pi.p, m->c_save.p + (size_t)NP * NP, (size_t)NP * sizeof(double), hipMemcpyDeviceToDevice));
+      HIPCHK(hipMemcpy(m->tab.p, m->c_save.p + (size_t)NP * NP + NP, n_tab * sizeof(double), hipMemcpyDeviceToDevice));
+      if (int rc = mstep_rebuild(m, tr, true, true)) return rc;
+      HIPCHK(hipDeviceSynchronize());
+      ++m->version;
+      return fail(TEHMM_ERR_ARG, std::string("tehmm_model_mstep: ") +
+                  ((status & TEHMM_CSTAT_EMIS_ZERO) ? "a forced emission row totals zero and nothing learned is left to "
+                                                      "scale (the reference asserts curTotal > 0)"
+                                                    : "a constrained value is not finite") +
+                  "; the parameters are those from before the call");
+    }
+  } else {
+    HIPCHK(hipDeviceSynchronize());
+  }
   ++m->version;
+  return TEHMM_OK;
+}
+
+// tehmm_model_set_constraints: the tables are checked, uploaded once and kept on the handle
+int tehmm_model_set_constraints(tehmm_model_t *m, const uint8_t *trans_mask, const double *trans_val,
+                                const uint8_t *start_mask, const double *start_val, const uint8_t *emis_mask,
+                                const double *emis_val, int trans_epsilons) {
+  if (!m || (trans_mask == nullptr) != (trans_val == nullptr) || (start_mask == nullptr) != (start_val == nullptr) ||
+      (emis_mask == nullptr) != (emis_val == nullptr))
+    return fail(TEHMM_ERR_ARG, "tehmm_model_set_constraints: NULL handle or a mask without its values");
+  if (m->N > 128)
+    return fail(TEHMM_ERR_UNSUPPORTED, "tehmm_model_set_constraints: N > 128 (no device-resident M-step)");
+  const int N = m->N, NP = m->NP, K = m->K, S = m->S;
+  // what the forced values alone decide (hmm.py:410-413, 471-472; emission.py:391-399, 410-419)
+  if (trans_mask)
+    for (int i = 0; i < N; ++i) {
+      double tgt = 1.0;
+      for (int j = 0; j < N; ++j)
+        if (trans_mask[(size_t)i * N + j]) tgt -= trans_val[(size_t)i * N + j];
+      if (!(tgt >= -TEHMM_DBL_EPS))
+        return fail(TEHMM_ERR_ARG, "tehmm_model_set_constraints: forced transitions of state " + std::to_string(i) +
+                                       " exceed 1 (or are not numbers)");
+    }
+  if (start_mask) {
+    double tgt = 1.0;
+    for (int i = 0; i < N; ++i)
+      if (start_mask[i]) tgt -= start_val[i];
+    if (!(tgt >= 0.0)) return fail(TEHMM_ERR_ARG, "tehmm_model_set_constraints: forced start probabilities exceed 1");
+  }
+  if (emis_mask)
+    for (int k = 0; k < K; ++k)
+      for (int j = 0; j < N; ++j) {
+        const uint8_t *mk = emis_mask + ((size_t)k * N + j) * S;
+        const double *vl = emis_val + ((size_t)k * N + j) * S;
+        if (m->rowcnt[k] < 2 || (mk[1] & 2)) continue;
+        double tgt = 1.0;
+        int forced = 0;
+        for (int s = 1; s < m->rowcnt[k]; ++s)
+          if (mk[s] & 1) { tgt -= vl[s]; ++forced; }
+        if (!(tgt >= 0.0))
+          return fail(TEHMM_ERR_ARG, "tehmm_model_set_constraints: forced emissions of track " + std::to_string(k) +
+                                         ", state " + std::to_string(j) + " exceed 1 (or are not numbers)");
+        if (forced == m->rowcnt[k] - 1 && tgt < 1.0)
+          return fail(TEHMM_ERR_ARG, "tehmm_model_set_constraints: every symbol of track " + std::to_string(k) +
+                                         ", state " + std::to_string(j) + " is forced: no symbol left for the leftover");
+      }
+  m->c_trans = m->c_start = m->c_emis = m->c_eps = false;
+  m->c_tmask.release(); m->c_tval.release();
+  m->c_smask.release(); m->c_sval.release();
+  m->c_emask.release(); m->c_eval.release();
+  if (!trans_mask && !start_mask && !emis_mask && !trans_epsilons) {
+    m->c_save.release();
+    m->c_status.release();
+    return TEHMM_OK;
+  }
+  if (trans_mask) {
+    HIPCHK(m->c_tmask.upload(trans_mask, (size_t)N * N));
+    HIPCHK(m->c_tval.upload(trans_val, (size_t)N * N));
+  }
+  if (start_mask) {
+    HIPCHK(m->c_smask.upload(start_mask, (size_t)N));
+    HIPCHK(m->c_sval.upload(start_val, (size_t)N));
+  }
+  if (emis_mask) {
+    HIPCHK(m->c_emask.upload(emis_mask, (size_t)K * N * S));
+    HIPCHK(m->c_eval.upload(emis_val, (size_t)K * N * S));
+  }
+  HIPCHK(m->c_save.alloc((size_t)NP * NP + NP + (size_t)(m->R + 1) * NP));
+  HIPCHK(m->c_status.alloc(1));
+  m->c_trans = trans_mask != nullptr;
+  m->c_start = start_mask != nullptr;
+  m->c_emis = emis_mask != nullptr;
+  m->c_eps = trans_epsilons != 0;
   return TEHMM_OK;
 }
 

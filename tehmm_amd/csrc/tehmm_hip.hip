@@ -307,6 +307,13 @@ struct tehmm_model {
   DBuf<double> qall[2];
   DBuf<int> qok[2];
   uint64_t q_version[2] = {~(uint64_t)0, ~(uint64_t)0};
+  // user constraints of the M-step (tehmm_model_set_constraints): uploaded once, applied by every tehmm_model_mstep.
+  // Masks / values in the caller's shapes ([N][N], [N], [K][N][S]); c_save = lt | pi | tab as they were before the
+  // M-step (what a failed one puts back); c_status: the word the constraint kernels raise.
+  DBuf<uint8_t> c_tmask, c_smask, c_emask;
+  DBuf<double> c_tval, c_sval, c_eval, c_save;
+  DBuf<int> c_status;
+  bool c_trans = false, c_start = false, c_emis = false, c_eps = false;
 };
 
 // workspace of the fused E-step, kept with the batch so that EM iterations reuse it
@@ -803,17 +810,10 @@ int tehmm_model_create(int N, int K, int S, const double *lt, const double *pi,
   m->normalize = normalize;
   const int NP = m->NP;
   // tables are [NP][NP]; padding states have -inf log-transitions / zero probability
-  std::vector<double> hlt((size_t)NP * NP, -INFINITY), hA((size_t)NP * NP, 0.0),
-      hAT((size_t)NP * NP, 0.0), hpi(NP, -INFINITY);
+  std::vector<double> hlt((size_t)NP * NP, -INFINITY), hpi(NP, -INFINITY);
   for (int i = 0; i < N; ++i) {
     hpi[i] = pi[i];
-    for (int j = 0; j < N; ++j) {
-      double l = lt[(size_t)i * N + j];
-      hlt[(size_t)i * NP + j] = l;
-      double a = std::exp(l);
-      hA[(size_t)i * NP + j] = a;
-      hAT[(size_t)j * NP + i] = a;
-    }
+    for (int j = 0; j < N; ++j) hlt[(size_t)i * NP + j] = lt[(size_t)i * N + j];
   }
   m->h_lt.assign(lt, lt + (size_t)N * N);
   int R = 0;
@@ -859,30 +859,18 @@ int tehmm_model_create(int N, int K, int S, const double *lt, const double *pi,
       for (int s = 0; s < m->rowcnt[k]; ++s)
         for (int j = 0; j < NP; ++j)
           hltab[(size_t)(m->ldsbase[k] + s) * NP + j] = htab[(size_t)(m->rowbase[k] + s) * NP + j];
-  std::vector<double> hltT((size_t)NP * NP, -INFINITY);
-  for (int i = 0; i < NP; ++i)
-    for (int j = 0; j < NP; ++j) hltT[(size_t)j * NP + i] = hlt[(size_t)i * NP + j];
-  auto group_major = [&](const std::vector<double> &src) {      // [f][o] -> [o / 4][f][o % 4]
-    std::vector<double> g((size_t)NP * NP);
-    for (int f = 0; f < NP; ++f)
-      for (int o = 0; o < NP; ++o) g[(size_t)TEHMM_TG(f, o, NP)] = src[(size_t)f * NP + o];
-    return g;
-  };
-  const std::vector<double> hltG = group_major(hlt), hAG = group_major(hA), hATG = group_major(hAT);
   hipError_t e = m->lt.upload(hlt.data(), hlt.size());
-  std::vector<float> hltP((size_t)NP * NP + NP + 2, 0.f);    // + lt[o][o] per output and lt[0][0] (segment-ratio P0)
-  for (int f = 0; f < NP; ++f)
-    for (int o = 0; o < NP; ++o) hltP[((size_t)(o >> 1) * NP + f) * 2 + (o & 1)] = (float)hlt[(size_t)f * NP + o];
-  for (int o = 0; o < N; ++o) hltP[(size_t)NP * NP + o] = (float)hlt[(size_t)o * NP + o];
-  hltP[(size_t)NP * NP + NP] = (float)hlt[0];
-  if (e == hipSuccess) e = m->ltG.upload(hltG.data(), hltG.size());
-  if (e == hipSuccess) e = m->ltP.upload(hltP.data(), hltP.size());
-  if (e == hipSuccess) e = m->AG.upload(hAG.data(), hAG.size());
-  if (e == hipSuccess) e = m->ATG.upload(hATG.data(), hATG.size());
-  if (e == hipSuccess) e = m->ltT.upload(hltT.data(), hltT.size());
+  // the copies derived from lt (layouts: k_model_layouts) are only allocated here; the kernel below fills them
+  const size_t nn = (size_t)NP * NP, nltP = nn + NP + 2;    // + lt[o][o] per output and lt[0][0] (segment-ratio P0)
+  if (e == hipSuccess) e = m->ltG.alloc(nn);
+  if (e == hipSuccess) e = m->ltP.alloc(nltP);
+  if (e == hipSuccess) e = hipMemset(m->ltP.p, 0, nltP * sizeof(float));
+  if (e == hipSuccess) e = m->AG.alloc(nn);
+  if (e == hipSuccess) e = m->ATG.alloc(nn);
+  if (e == hipSuccess) e = m->ltT.alloc(nn);
   if (e == hipSuccess) e = m->ltab.upload(hltab.data(), hltab.size());
-  if (e == hipSuccess) e = m->A.upload(hA.data(), hA.size());
-  if (e == hipSuccess) e = m->AT.upload(hAT.data(), hAT.size());
+  if (e == hipSuccess) e = m->A.alloc(nn);
+  if (e == hipSuccess) e = m->AT.alloc(nn);
   if (e == hipSuccess) e = m->pi.upload(hpi.data(), hpi.size());
   htab.resize(htab.size() + 64, 0.0);     // (slack: k_emis_gain_lane3's last wave reads a full slice of states past NP)
   if (e == hipSuccess) e = m->tab.upload(htab.data(), htab.size());
@@ -890,6 +878,11 @@ int tehmm_model_create(int N, int K, int S, const double *lt, const double *pi,
     delete m;
     return fail(TEHMM_ERR_HIP, std::string("tehmm_model_create: ") + hipGetErrorString(e));
   }
+  // the copies derived from lt are written by the kernel the M-step rebuilds them with: exp() of the device and of the
+  // host may differ in the last bit, and a handle has to be the same function of its parameters whether they came from
+  // the caller or from an M-step (build_ptab below checks the launch and synchronises)
+  hipLaunchKernelGGL(k_model_layouts, dim3(grid_for((int64_t)NP * NP, 256)), dim3(256), 0, 0, NP,
+                     (const double *)m->lt.p, m->ltT.p, m->A.p, m->AT.p, m->ltG.p, m->AG.p, m->ATG.p, m->ltP.p);
   if (int rc = build_ptab(m)) {
     delete m;
     return rc;

@@ -189,6 +189,108 @@ class IndependentMultinomialEmissionModel(object):
         self.maximize(obsStats, trackData.getTrackList())
         self.validate()
 
+    def applyUserEmissions(self, userEmLines, stateMap, trackList, record=None):
+        """emission.py:347-438: the emissions named in the lines (STATE TRACK SYMBOL PROB) are set and the other symbols
+        of each (track, state) row brought to the mass they leave.  The closing myLog(exp(.)) runs over the WHOLE
+        table: every -1e6 that maximize() wrote becomes myLog's zero value, on all tracks.  With a dict as `record`
+        the lines are parsed and everything the forced values alone decide is checked, the forced cells are noted in
+        it ("emis_mask" uint8 [K][N][S], "emis_val" [K][N][S] probabilities, "emis_gauss" [(track, state, mu, sigma)])
+        and nothing else happens (call it on a copy: the lines are applied to the copy's table on the way)."""
+        logProbs = self.getLogProbs()
+        mask = np.zeros(logProbs.shape, dtype=np.int8)
+        if record is not None:
+            record["emis_gauss"] = []
+        for line in userEmLines:
+            if len(line.lstrip()) > 0 and line.lstrip()[0] != "#":
+                toks = line.split()
+                assert len(toks) == 4
+                stateName, trackName = toks[0], toks[1]
+                if not stateMap.has(stateName):
+                    raise RuntimeError("User Emission: State %s not found" % stateName)
+                state = stateMap.getMap(stateName)
+                track = trackList.getTrackByName(trackName)
+                if track is None:
+                    raise RuntimeError("Track %s (in user emissions) not found" % trackName)
+                self.applyUserEmissionLine(track, state, toks, logProbs, mask)
+                if record is not None and track.getDist() == "gaussian" and hasattr(self, "gaussParams"):
+                    record["emis_gauss"].append((track.getNumber(), state, float(toks[2]), float(toks[3])))
+        probs = np.exp(logProbs)                   # easier outside log space
+        for track in range(self.getNumTracks()):
+            if trackList.getTrackByNumber(track).getDist() == "gaussian":
+                continue
+            trackName = trackList.getTrackByNumber(track).getName()
+            for state in range(self.getNumStates()):
+                curTotal = 0.0                     # mass of the learned symbols
+                tgtTotal = 1.0                     # their mass after the correction
+                for symbol in self.getTrackSymbols(track):
+                    if mask[track, state, symbol] == 1:
+                        tgtTotal -= probs[track, state, symbol]
+                    else:
+                        curTotal += probs[track, state, symbol]
+                    if tgtTotal < 0.:
+                        raise RuntimeError("User defined prob from state %s for track %s exceeds 1 by %e"
+                                           % (stateMap.getMapBack(state), trackName, 0. - tgtTotal))
+                numUnmasked = self.numSymbolsPerTrack[track] - np.sum(mask[track, state])
+                if record is not None:
+                    # an empty learned set has mass zero whatever was learned: the additive branch below, decided here
+                    if numUnmasked == 0 and tgtTotal < 1.:
+                        raise RuntimeError("User defined emission prob for state %s track %s total less than 1 (%f)"
+                                           "and there are no remaining symbols to assign leftover probability to"
+                                           % (stateMap.getMapBack(state), trackName, tgtTotal))
+                    continue
+                # the forced symbols total less than 1 and nothing is left to scale: (1, 0, 0, 0) -> (0.95, 0, 0, 0)
+                additive = False
+                if curTotal == 0. and tgtTotal < 1.:
+                    additive = True
+                    if numUnmasked == 0:
+                        raise RuntimeError("User defined emission prob for state %s track %s total less than 1 (%f)"
+                                           "and there are no remaining symbols to assign leftover probability to"
+                                           % (stateMap.getMapBack(state), trackName, tgtTotal))
+                    addAmt = (1. - tgtTotal) / float(numUnmasked)
+                else:
+                    assert curTotal > 0.
+                    multAmt = tgtTotal / curTotal
+                for symbol in self.getTrackSymbols(track):
+                    if mask[track, state, symbol] == 0:
+                        if tgtTotal == 0.:
+                            probs[track, state, symbol] = 0.
+                        elif additive is False:
+                            probs[track, state, symbol] *= multAmt
+                        else:
+                            probs[track, state, symbol] += addAmt
+        if record is not None:
+            record["emis_mask"] = mask.astype(np.uint8)
+            record["emis_val"] = np.where(mask == 1, probs, 0.0)
+            return
+        self.logProbs = myLog(probs)
+        self.validate()
+
+    def applyUserEmissionLine(self, track, state, toks, logProbs, mask):
+        """emission.py:440-470: one STATE TRACK SYMBOL PROB line into logProbs and mask."""
+        from .track import BinaryMap
+        symbolMap = track.getValueMap()
+        trackName = track.getName()
+        track = track.getNumber()
+        symbolName = toks[2]
+        prob = float(toks[3])
+        if isinstance(symbolMap, BinaryMap):
+            # the binary map tells None from everything else
+            if symbolName == "0" or symbolName == "None":
+                symbolName = None
+            symbol = symbolMap.getMap(symbolName)
+        else:
+            try:                                   # (scaling a non-numeric value raises)
+                hasSymbol = symbolMap.has(symbolName)
+                symbol = symbolMap.getMap(symbolName)
+            except Exception:
+                hasSymbol = False
+                symbol = symbolMap.getMissingVal()
+            if not hasSymbol:
+                logger.warning("Track %s Symbol %s not found in data (setting as null value)" % (trackName, symbolName))
+        assert symbol in self.getTrackSymbols(track)
+        logProbs[track, state, symbol] = myLog(prob)
+        mask[track, state, symbol] = 1
+
     def validate(self):
         """emission.py:269-291: every state's distribution over symbol vectors sums to 1."""
         numSymbols = reduce(lambda x, y: max(x, 1) * max(y, 1), self.numSymbolsPerTrack, 1)
@@ -278,3 +380,14 @@ class IndependentMultinomialAndGaussianEmissionModel(IndependentMultinomialEmiss
     def maximize(self, obsStats, trackList):
         super(IndependentMultinomialAndGaussianEmissionModel, self).maximize(obsStats)
         self.makeGaussian(trackList)
+
+    def applyUserEmissionLine(self, track, state, toks, logProbs, mask):
+        """emission.py:595-615: on a gaussian track the line reads STATE TRACK MEAN STDEV; the row is filled from the
+        two and masked whole."""
+        if track.getDist() != "gaussian":
+            return super(IndependentMultinomialAndGaussianEmissionModel, self).applyUserEmissionLine(
+                track, state, toks, logProbs, mask)
+        self.gaussParams[track.getNumber(), state, 0] = float(toks[2])
+        self.gaussParams[track.getNumber(), state, 1] = float(toks[3])
+        self.applyGaussian(track, state, logProbs)
+        mask[track.getNumber(), state, :] = 1

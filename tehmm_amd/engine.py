@@ -81,6 +81,23 @@ class HipModel(object):
                                                  ptr(gp, f64p)), "tehmm_model_mstep")
         return gp
 
+    def set_constraints(self, trans=None, start=None, emission=None, trans_epsilons=False):
+        """The user constraints every later mstep() applies (tehmm_model_set_constraints): each of trans [N,N],
+        start [N], emission [K,N,S] is a (mask, values) pair or None; values are probabilities.  Emission mask bit 1
+        marks the cells of gaussian tracks.  All None and no epsilons clears them."""
+        args = []
+        for pair, shape in ((trans, (self.N, self.N)), (start, (self.N,)), (emission, (self.K, self.N, self.S))):
+            if pair is None:
+                args += [None, None]
+                continue
+            mask = np.ascontiguousarray(pair[0], dtype=np.uint8)
+            vals = np.ascontiguousarray(pair[1], dtype=np.float64)
+            assert mask.shape == shape and vals.shape == shape
+            args += [mask, vals]
+        _lib.check(_lib.load().tehmm_model_set_constraints(
+            self._h, ptr(args[0], _lib.u8p), ptr(args[1], f64p), ptr(args[2], _lib.u8p), ptr(args[3], f64p),
+            ptr(args[4], _lib.u8p), ptr(args[5], f64p), int(bool(trans_epsilons))), "tehmm_model_set_constraints")
+
     def get_params(self, log_probs_like):
         """(log_transmat [N,N], log_startprob [N], logProbs [K,N,S]) of the handle; the padding cells of
         logProbs are taken from `log_probs_like`."""
@@ -102,6 +119,9 @@ class HipModel(object):
                                                  ptr(obs_stats, f64p), ctypes.byref(lp)),
                    "tehmm_estep_batch")
         return lp.value
+
+
+DeviceModel = HipModel          # (the handle seen from the device-resident training loop)
 
 
 class DeviceStats(object):

@@ -52,10 +52,10 @@ class MultitrackHmm(BaseHMM):
         self.current_iteration = None
         self.last_forward_log_prob = None
         self.last_forward_log_prob_it = -1
-        if forceUserTrans is not None or forceUserEmissions is not None or forceUserStart is not None:
-            raise NotImplementedError("forceUser{Trans,Emissions,Start} text files are outside the "
-                                      "hot path this package replaces")
-        self.forceUserTrans = self.forceUserEmissions = self.forceUserStart = None
+        # user files (as line lists) re-applied after every M-step (hmm.py:123-137)
+        self.forceUserTrans = _read_lines(forceUserTrans)
+        self.forceUserEmissions = _read_lines(forceUserEmissions)
+        self.forceUserStart = _read_lines(forceUserStart)
         self.maxProb = maxProb
         self.best_forward_log_prob = None
         self.bestCopy = None
@@ -200,6 +200,110 @@ class MultitrackHmm(BaseHMM):
 
     def getStartProbs(self):
         return self.startprob_
+
+    def getLastLogProb(self):
+        return self.last_forward_log_prob
+
+    # ------------------------------------------------------------------ user parameters (hmm.py:348-488)
+    def applyUserEmissions(self, userEmLines, record=None):
+        """hmm.py:348-355.  record: see emissionModel.applyUserEmissions."""
+        assert self.stateNameMap is not None
+        assert self.trackList is not None
+        assert self.emissionModel is not None
+        self.emissionModel.applyUserEmissions(userEmLines, self.stateNameMap, self.trackList, record=record)
+
+    def applyUserTrans(self, userTransLines, record=None):
+        """hmm.py:357-429: the transitions named in the lines (FROM TO PROB) are set, the other cells of each row
+        scaled to the mass the named ones leave.  With a dict as `record` the lines are parsed and checked, the forced
+        cells noted in it ("trans_mask" uint8 [N][N], "trans_val" [N][N]) and the model left alone: the tables of the
+        device M-step come from the same parser."""
+        N = self.n_components
+        mask = np.zeros((N, N), dtype=np.int8)
+        transMat = self.transmat_
+        catMap = self.stateNameMap
+        for toks in _user_lines(userTransLines):
+            assert len(toks) == 3
+            prob = float(toks[2])
+            fromState, toState = toks[0], toks[1]
+            if not catMap.has(fromState) or not catMap.has(toState):
+                raise RuntimeError("Cannot apply transition %s->%s to model since at least one of the states was "
+                                   "not found in the supervised data." % (fromState, toState))
+            fid, tid = catMap.getMap(fromState), catMap.getMap(toState)
+            mask[fid, tid] = 1
+            transMat[fid, tid] = prob
+        for fid in range(N):
+            curTotal = 0.0                         # mass of the learned cells
+            tgtTotal = 1.0                         # their mass after the scaling
+            for tid in range(N):
+                if mask[fid, tid] == 1:
+                    tgtTotal -= transMat[fid, tid]
+                else:
+                    curTotal += transMat[fid, tid]
+            if tgtTotal < -EPSILON:
+                raise RuntimeError("User defined probability %f from state %s exceeds 1"
+                                   % (tgtTotal, catMap.getMapBack(fid)))
+            if record is not None:
+                continue
+            for tid in range(N):
+                if mask[fid, tid] == 0:
+                    if tgtTotal == 0.:
+                        transMat[fid, tid] = 0.
+                    else:
+                        transMat[fid, tid] *= (tgtTotal / curTotal)
+        if record is not None:
+            record["trans_mask"] = mask.astype(np.uint8)
+            record["trans_val"] = np.where(mask == 1, transMat, 0.0)
+            return
+        self.numZeroInitEdges = int(np.sum(transMat <= EPSILON))       # zero edges, for the BIC
+        self.transmat_ = transMat                  # (the setter: myLog, transMatEpsilons)
+
+    def applyUserStarts(self, userStartLines, record=None):
+        """hmm.py:432-488 (STATE PROB lines); `record` as applyUserTrans ("start_mask" [N], "start_val" [N]).  The
+        reference counts the zeros into `numZeroInitStart`, an attribute that does not exist, and dies with
+        AttributeError at the first start probability below EPSILON; here they are counted into numZeroInitStarts
+        (quirk Q23)."""
+        startProbs = self.startprob_
+        N = self.n_components
+        mask = np.zeros(startProbs.shape, dtype=np.int8)
+        for toks in _user_lines(userStartLines):
+            assert len(toks) == 2
+            stateName = toks[0]
+            prob = float(toks[1])
+            if not self.stateNameMap.has(stateName):
+                raise RuntimeError("State %s not found in supervised data" % stateName)
+            state = self.stateNameMap.getMap(stateName)
+            startProbs[state] = prob
+            mask[state] = 1
+        curTotal = 0.0
+        tgtTotal = 1.0
+        for state in range(N):
+            if mask[state] == 1:
+                tgtTotal -= startProbs[state]
+            else:
+                curTotal += startProbs[state]
+            if tgtTotal < 0.:
+                raise RuntimeError("User defined start probabiliies exceed 1")
+        if record is not None:
+            record["start_mask"] = mask.astype(np.uint8)
+            record["start_val"] = np.where(mask == 1, startProbs, 0.0)
+            return
+        for state in range(N):
+            if mask[state] == 0:
+                if tgtTotal == 0.:
+                    startProbs[state] = 0.
+                else:
+                    startProbs[state] *= (tgtTotal / curTotal)
+        self.numZeroInitStarts = int(np.sum(startProbs < EPSILON))
+        self.startprob_ = startProbs
+
+    def _apply_forced(self):
+        """The three force lists in the reference's order (hmm.py:608-614)."""
+        if self.forceUserTrans is not None:
+            self.applyUserTrans(self.forceUserTrans)
+        if self.forceUserEmissions is not None:
+            self.applyUserEmissions(self.forceUserEmissions)
+        if self.forceUserStart is not None:
+            self.applyUserStarts(self.forceUserStart)
 
     def getNumFreeParameters(self):
         """Number of free, learnable parameters (hmm.py:490-520; feeds the BIC of teHmmEval.py:216-234)."""
@@ -467,6 +571,7 @@ class MultitrackHmm(BaseHMM):
         if 'e' in params:
             self.emissionModel.maximize(stats['obs'], self.trackList)
         self.current_iteration += 1
+        self._apply_forced()                       # whether or not the parameter is in `params`
         self.validate()
 
     def fit(self, obs, shard_lengths=None, **kwargs):
@@ -488,7 +593,7 @@ class MultitrackHmm(BaseHMM):
         from .emission import (IndependentMultinomialAndGaussianEmissionModel,
                                IndependentMultinomialEmissionModel)
         em = self.emissionModel
-        if os.environ.get("TEHMM_DEVICE_EM", "1") == "0" or self.transMatEpsilons:
+        if os.environ.get("TEHMM_DEVICE_EM", "1") == "0":
             return False
         if type(em) not in (IndependentMultinomialEmissionModel, IndependentMultinomialAndGaussianEmissionModel):
             return False
@@ -536,6 +641,7 @@ class MultitrackHmm(BaseHMM):
         arrays = {i: (tables[i].getNumPyArray() if isinstance(tables[i], TrackTable)
                       else np.ascontiguousarray(tables[i])) for i in mine}
         ratios = {i: self.emissionModel.getSegmentRatios(tables[i]) for i in mine}
+        cons = self._device_constraints()              # (parsed before anything is on the device: a bad file raises here)
         hm = self._device_model()
         batches = []
         for has_r in (True, False):
@@ -550,7 +656,13 @@ class MultitrackHmm(BaseHMM):
         stats = DeviceStats(hm)
         gauss = self._gaussian_spec()
         logprob = []
+        constrained = False
+        msteps = 0
         try:
+            if cons is not None:
+                # the handle is cached and evaluation reuses it: the tables are taken off again below
+                constrained = True
+                hm.set_constraints(**{k: cons[k] for k in ("trans", "start", "emission", "trans_epsilons")})
             for i in range(copy.deepcopy(self.n_iter)):
                 stats.zero()
                 loc_idx, loc_lp = [], []
@@ -591,12 +703,32 @@ class MultitrackHmm(BaseHMM):
                 if gp is not None and do_e:
                     for g, k in enumerate(gauss[0]):
                         self.emissionModel.gaussParams[k] = gp[g]
+                if cons is not None:
+                    # (the refit reports what it fitted to the statistics; a forced row holds the user's pair)
+                    for k, j, mu, sigma in cons["gauss"]:
+                        self.emissionModel.gaussParams[k, j] = (mu, sigma)
+                msteps += 1
                 self.current_iteration += 1
         finally:
             for _, _, hb in batches:
                 hb.close()
-            self._pull_params(hm)
-            stats.close()
+            cleared = False
+            try:
+                if constrained:
+                    hm.set_constraints()
+                cleared = True
+            finally:                                   # (whatever the clearing does: the host model and the buffer)
+                try:
+                    self._pull_params(hm)
+                    if not cleared:
+                        self._dev = None               # (evaluation must not reuse a handle that still holds them)
+                finally:
+                    stats.close()
+        if msteps > 0 and not fallback:                # the counts applyUserTrans / applyUserStarts keep for the BIC
+            if self.forceUserTrans is not None:
+                self.numZeroInitEdges = int(np.sum(self.transmat_ <= EPSILON))
+            if self.forceUserStart is not None:
+                self.numZeroInitStarts = int(np.sum(self.startprob_ < EPSILON))
         if fallback:
             keep = self.init_params
             self.init_params = ""                      # (_init has run; the parameters are the ones it left)
@@ -607,6 +739,32 @@ class MultitrackHmm(BaseHMM):
                 self.init_params = keep
         self.validate()
         return self
+
+    def _device_constraints(self):
+        """What tehmm_model_set_constraints takes, from the force line lists and transMatEpsilons: the host parsers run
+        in their recording mode on a copy of the model (same lines, same errors, one parser).  None when the model
+        has neither.  "gauss": the forced (track, state, mu, sigma)."""
+        eps = self.transMatEpsilons is True
+        if self.forceUserTrans is None and self.forceUserEmissions is None and self.forceUserStart is None and not eps:
+            return None
+        rec = {}
+        dev, self._dev = self._dev, None
+        probe = copy.deepcopy(self)
+        self._dev = dev
+        if self.forceUserTrans is not None:
+            probe.applyUserTrans(self.forceUserTrans, record=rec)
+        if self.forceUserEmissions is not None:
+            probe.applyUserEmissions(self.forceUserEmissions, record=rec)
+            for t in self.trackList:
+                if t.getDist() == "gaussian":
+                    rec["emis_mask"][t.getNumber()] |= 2       # (the track's rows take no part in the rescale)
+        if self.forceUserStart is not None:
+            probe.applyUserStarts(self.forceUserStart, record=rec)
+
+        def pair(name):
+            return (rec[name + "_mask"], rec[name + "_val"]) if name + "_mask" in rec else None
+        return {"trans": pair("trans"), "start": pair("start"), "emission": pair("emis"), "trans_epsilons": eps,
+                "gauss": rec.get("emis_gauss", [])}
 
     def _gaussian_spec(self):
         """(track indices, values [n][S], uniform mix) of the gaussian tracks, or None."""
@@ -639,7 +797,9 @@ class MultitrackHmm(BaseHMM):
             transmat = np.tile(1.0 / self.n_components, (self.n_components, self.n_components))
         transmat = np.asarray(transmat, dtype=np.float64)
         if not np.all(transmat) and self.transMatEpsilons is True:
-            transmat = normalize(transmat.copy(), axis=1)
+            # the reference calls normalize(transmat, axis=1) and drops what it returns: what takes effect is that
+            # function's in-place `+= eps`; the rows are not divided by their sums (quirk Q24)
+            transmat = transmat + EPSILON
         if transmat.shape != (self.n_components, self.n_components):
             raise ValueError('transmat must have shape (n_components, n_components)')
         if not np.all(np.allclose(np.sum(transmat, axis=1), 1.0)):
@@ -719,6 +879,20 @@ class MultitrackHmm(BaseHMM):
         d = dict(self.__dict__)
         d["_dev"] = None            # device handles are not picklable / copyable
         return d
+
+
+def _read_lines(path):
+    if path is None:
+        return None
+    with open(path) as f:
+        return f.readlines()
+
+
+def _user_lines(lines):
+    """The token lists of the lines of a user file that are neither blank nor comments."""
+    for line in lines:
+        if len(line.lstrip()) > 0 and line.lstrip()[0] != "#":
+            yield line.split()
 
 
 def _py2_gt(a, b):

@@ -90,6 +90,10 @@ def saveModel(path, hmm):
                 "last_forward_log_prob": hmm.last_forward_log_prob,
                 "last_forward_log_prob_it": int(hmm.last_forward_log_prob_it)},
     }
+    force = {"trans": hmm.forceUserTrans, "emissions": hmm.forceUserEmissions, "start": hmm.forceUserStart}
+    if any(v is not None for v in force.values()):
+        # (optional key: the force line lists travel with the model, as they do in the reference's pickle)
+        meta["forceUser"] = {k: None if v is None else [str(x) for x in v] for k, v in force.items()}
     with open(path, "wb") as f:
         np.savez(f, format=np.asarray(FORMAT), log_transmat=hmm._log_transmat,
                  log_startprob=hmm._log_startprob,
@@ -138,6 +142,10 @@ def loadModel(path):
                             fixTrans=h["fixTrans"], fixEmission=h["fixEmission"], fixStart=h["fixStart"],
                             transMatEpsilons=h["transMatEpsilons"], maxProb=h["maxProb"], maxProbCut=h["maxProbCut"])
         hmm.trackList = tl
+        force = meta.get("forceUser") or {}
+        hmm.forceUserTrans = force.get("trans")
+        hmm.forceUserEmissions = force.get("emissions")
+        hmm.forceUserStart = force.get("start")
         # (transmat_ / startprob_ are views of the log tables, hmm.py:622-666: zeros stay -1e100)
         hmm._log_transmat = z["log_transmat"].copy()
         hmm._log_startprob = z["log_startprob"].copy()
