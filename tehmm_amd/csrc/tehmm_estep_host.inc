@@ -344,8 +344,9 @@ static EstepOutcome estep_fused(tehmm_model_t *m, tehmm_batch_t *b, const EvalKn
   (void)hipMemsetAsync(b->dead.p, 0, (size_t)(b->n + 1) * sizeof(int), st);
   (void)hipMemsetAsync(sw.stats.p + 2, 0, 4 * sizeof(int), st);
   int rc = TEHMM_OK;
+  const bool tail = fused_tail_runs(m, kn.fused_tail);
   nt_dispatch(m->NP, [&](auto nt) {
-    rc = launch_fused_fb<nt>(b, m, iv, em, fc, WuF, st, b->ev[kEvFwdEnd], b->ev[kEvBwdEnd], true);
+    rc = launch_fused_fb<nt>(b, m, iv, em, fc, WuF, st, b->ev[kEvFwdEnd], b->ev[kEvBwdEnd], tail, true);
   });
   if (rc) return rc;
   (void)hipEventRecord(b->ev[kEvFusedChainEnd], st);
@@ -360,6 +361,8 @@ static EstepOutcome estep_fused(tehmm_model_t *m, tehmm_batch_t *b, const EvalKn
   add_stage(b, "estep_reduce", kEvFusedChainEnd, kEvFusedReduceEnd);
   stage_times(b);
   if ((rc = add_chain_counters(b))) return rc;
+  // (only where the knob is set: callers compare the timing list of a fused E-step name by name, in order)
+  if (kn.fused_tail_set) add_counter(b, "count:fused_tail", tail ? 1 : 0);
   if ((rc = estep_results(b, b->fwd_lp.p, b->dead.p, nullptr, lp_out, dead_out))) return rc;
   return EstepOutcome::Ran;
 }

@@ -125,6 +125,49 @@ __device__ __forceinline__ double item_max4(double t) {
   return fmax(__hiloint2double((int)d[0], (int)c[0]), __hiloint2double((int)d[1], (int)c[1]));
 }
 
+// The tail form of the product (TAIL; linear domain, NT = 4 mod 16, at least one full row tile: NT = 20 and 36).  The last
+// row tile of D' = T V holds four states and twelve pads, and a v_mfma_f64_16x16x4_f64 takes its 64 pipe cycles whatever
+// it multiplies: at NT = 36 nine of the 27 MFMAs of a step do a quarter of their nominal work.  The four rows are computed
+// on the vector pipe instead.  Lane (kq, c) holds tf[RT - 1][s] = T[16 (RT - 1) + c][4 s + kq] (zero for c >= 4), so lane
+// (kq, j) of that register IS the coefficient every lane of row kq needs for tail output j: a DPP row broadcast feeds it
+// to the FMA, no register and no LDS holds it per lane,
+//     P[j] += T[16 (RT - 1) + j][4 s + kq] * v[s]        j = 0 .. 3, s = 0 .. KS - 1
+// (row_newbcast is the one DPP control of the 64-bit ALU; v_fmac_f64 is VOP2 and takes it on src0).  The DPP read needs
+// the whole wave enabled -- so do the MFMAs beside it -- and no VALU write of its source in the two instructions before
+// it: the coefficients are loop-invariant.  Behind the k loop every lane holds four partial sums over its own KS states;
+// lane (kq, item) needs the total of output kq: fused_tail_scatter.
+// The DPP FMA is inline assembly, so the compiler inserts no hazard nops for it: after an edit or a compiler change check the
+// assembly again with  tools/isamix.py REGEX ASMFILE --loop --dpp-hazards  (profiles/r10_loop_mix.txt is its output).
+#define TEHMM_TAIL_FMA(acc, coef, x, j) \
+  asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #j " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(coef), "v"(x))
+constexpr bool fused_tail_nt(int nt) { return nt % 16 == 4 && nt > 16 && nt <= TEHMM_FUSED_2W; }
+template <int NT, bool LOGDOM>
+struct FusedTail {
+  static constexpr bool ok = !LOGDOM && fused_tail_nt(NT);
+};
+// element k of the product D' for this lane (state kq + 4 k): from the row tiles, or -- TAIL, the lane's last state -- the tail sum
+#define TEHMM_FUSED_PROD(k) ((TAIL && (k) == KS - 1) ? tail : acc[(TAIL && (k) == KS - 1) ? 0 : (k) >> 2][(k) & 3])
+__device__ __forceinline__ void fused_tail_fma(double (&p)[4], double coef, double x) {
+  TEHMM_TAIL_FMA(p[0], coef, x, 0);
+  TEHMM_TAIL_FMA(p[1], coef, x, 1);
+  TEHMM_TAIL_FMA(p[2], coef, x, 2);
+  TEHMM_TAIL_FMA(p[3], coef, x, 3);
+}
+// Reduce-scatter of the four partial sums over the four rows of the wave: v_permlane32_swap exchanges lanes 32-63 of its
+// first operand with lanes 0-31 of its second, v_permlane16_swap the odd rows of its first with the even rows of its second.
+__device__ __forceinline__ double fused_tail_scatter(const double (&p)[4]) {
+  const auto al = __builtin_amdgcn_permlane32_swap(__double2loint(p[0]), __double2loint(p[2]), false, false);
+  const auto ah = __builtin_amdgcn_permlane32_swap(__double2hiint(p[0]), __double2hiint(p[2]), false, false);
+  const auto bl = __builtin_amdgcn_permlane32_swap(__double2loint(p[1]), __double2loint(p[3]), false, false);
+  const auto bh = __builtin_amdgcn_permlane32_swap(__double2hiint(p[1]), __double2hiint(p[3]), false, false);
+  // lanes 0-31: outputs 0 and 1, lanes 32-63: outputs 2 and 3, each summed over rows r and r + 2
+  const double r0 = __hiloint2double((int)ah[0], (int)al[0]) + __hiloint2double((int)ah[1], (int)al[1]);
+  const double r1 = __hiloint2double((int)bh[0], (int)bl[0]) + __hiloint2double((int)bh[1], (int)bl[1]);
+  const auto cl = __builtin_amdgcn_permlane16_swap(__double2loint(r0), __double2loint(r1), false, false);
+  const auto ch = __builtin_amdgcn_permlane16_swap(__double2hiint(r0), __double2hiint(r1), false, false);
+  return __hiloint2double((int)ch[0], (int)cl[0]) + __hiloint2double((int)ch[1], (int)cl[1]);   // row kq: output kq
+}
+
 // The wave's window on its index records: two 3 KB LDS buffers, the record of the next block on its way
 // through three registers per lane.  dir = +1 (forward pass: blocks ascend) or -1.
 typedef unsigned int fused_u4 __attribute__((ext_vector_type(4)));
@@ -442,13 +485,15 @@ __global__ __launch_bounds__(256) void k_fused_rowindex(IntervalTab iv, LaneGeom
 // (item-interleaved), pre / end vectors, cumulative log-scale records; the emission rows are computed here.
 // Extended step e <-> position t0 - Wu + e; the pass covers e = 0 .. L + Wu - 1.
 // ------------------------------------------------------------------------------------------
-template <int NT, bool LOGDOM>
+template <int NT, bool LOGDOM, bool TAIL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= TEHMM_FUSED_2W ? 2 : 1, NT <= TEHMM_FUSED_2W ? 2 : 1)))
 void k_fused_fwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu,
                  const double *__restrict__ tab /* A, [NT][NT] row-major */, float *al32, double *chkf, double *pre,
                  double *end, double *slog32) {
   using G = FusedGeom<NT>;
   constexpr int KS = G::KS, RT = G::RT;
+  static_assert(!TAIL || FusedTail<NT, LOGDOM>::ok, "no tail form at this state count");
+  constexpr int RM = TAIL ? RT - 1 : RT;                 // row tiles on the matrix cores
   extern __shared__ double fused_lds[];
   fused_stage<NT>(ft, fused_lds);
   __syncthreads();
@@ -520,18 +565,23 @@ void k_fused_fwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
     }
     FST(3);
     // the product on the matrix cores, the next position's emission row gathered between its instructions
-    lane_d4 acc[RT];
+    lane_d4 acc[RM];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = (lane_d4){0.0, 0.0, 0.0, 0.0};
+    for (int rt = 0; rt < RM; ++rt) acc[rt] = (lane_d4){0.0, 0.0, 0.0, 0.0};
+    double pt[4] = {0.0, 0.0, 0.0, 0.0};  // TAIL: the partial sums of the last four state rows (see TEHMM_TAIL_FMA)
     // (the gather of position s + 1 was begun before the previous step's stores: vector-memory waits complete
     //  in issue order, and the first table load must not queue up behind them)
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(tf[rt][k], v[k], acc[rt], 0, 0, 0);
+      for (int rt = 0; rt < RM; ++rt) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(tf[rt][k], v[k], acc[rt], 0, 0, 0);
+      if constexpr (TAIL) fused_tail_fma(pt, tf[RT - 1][k], v[k]);
       es.slot(k);
       __builtin_amdgcn_sched_barrier(0);
     }
+    double tail = 0.0;
+    if constexpr (TAIL) tail = fused_tail_scatter(pt);
+    (void)tail;
     FST(0);
     double qn[KS], msn = 0.0;
     es.finish(N, qn, msn);
@@ -540,7 +590,7 @@ void k_fused_fwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
     double t = 0.0;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-      a[k] = acc[k >> 2][k & 3] * q[k];
+      a[k] = TEHMM_FUSED_PROD(k) * q[k];
       t += a[k];
     }
     t = item_sum4(t);
@@ -602,7 +652,7 @@ void k_fused_fwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
 // wz_t = w_{t+1} * scale_t / G_t, the row that makes xi_t(i, j) = alpha'_t[i] A[i][j] wz_t[j] sum to one
 // (_hmm.pyx:62-117 in the scaled linear domain; G_t = sum_j alpha'_t[j] beta_t[j], scale_t the power of two
 // that normalised beta_t): k_estep_reduce turns the three float rows of a position into the statistics.
-template <int NT, bool LOGDOM, bool EPS, bool ESTEP = false>
+template <int NT, bool LOGDOM, bool EPS, bool ESTEP = false, bool TAIL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT <= TEHMM_FUSED_2W ? 2 : 1, NT <= TEHMM_FUSED_2W ? 2 : 1)))
 void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu,
                  const double *__restrict__ tab /* A, [NT][NT] row-major */, const float *__restrict__ al32,
@@ -610,6 +660,8 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
                  double *sink = nullptr /* [tiles][64]: where the masked elements of the posterior stores go */) {
   using G = FusedGeom<NT>;
   constexpr int KS = G::KS, RT = G::RT;
+  static_assert(!TAIL || FusedTail<NT, LOGDOM>::ok, "no tail form at this state count");
+  constexpr int RM = TAIL ? RT - 1 : RT;                 // row tiles on the matrix cores
   extern __shared__ double fused_lds[];
   fused_stage<NT>(ft, fused_lds);
   __syncthreads();
@@ -641,7 +693,15 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
   for (int s = 0; s < KS; ++s) v[s] = 0.0;
   const int64_t prow0 = (iv.out0[id] + t0) * N;       // posterior row of the item's first position
   auto vec_out = [&](double *dst) {
-    const int64_t po = ((((item >> 6) * NT) + kq) << 6) + (item & 63);
+    // (TAIL: item >> 6 = tile >> 2 is the same in every lane; said so, the offset needs no vector register across the
+    //  loop beyond the lane number -- the three it took otherwise are the ones this form is short of.  The scalar form is
+    //  right for every instantiation; the other ones keep the per-lane form ONLY so that their code stays the parent's,
+    //  instruction for instruction and register for register, and the change is confined to what was measured)
+    int64_t po;
+    if constexpr (TAIL)
+      po = ((((int64_t)(__builtin_amdgcn_readfirstlane(tile) >> 2) * NT) + kq) << 6) + (((tile & 3) << 4) | (lane & 15));
+    else
+      po = ((((item >> 6) * NT) + kq) << 6) + (item & 63);
 #pragma unroll
     for (int s = 0; s < KS; ++s) dst[po + ((int64_t)(4 * s) << 6)] = v[s];
   };
@@ -744,9 +804,10 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
   for (int s = L + Wu - 1; s >= 0; --s) {
     if (s == L - 1 && run) vec_out(pre);               // v = w_{t0+L} after the warm-up
     FST(3);
-    lane_d4 acc[RT];
+    lane_d4 acc[RM];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = (lane_d4){0.0, 0.0, 0.0, 0.0};
+    for (int rt = 0; rt < RM; ++rt) acc[rt] = (lane_d4){0.0, 0.0, 0.0, 0.0};
+    double pt[4] = {0.0, 0.0, 0.0, 0.0};  // TAIL: the partial sums of the last four state rows (see TEHMM_TAIL_FMA)
     // (the gather of position s - 1 was begun before the previous step's stores, see k_fused_fwd)
     // alpha' row of this position (official range only; floats, five float2 per lane)
     // (loaded at EVERY step, the warm-up steps read the row of position L - 1 for nothing: a fixed number of
@@ -767,7 +828,8 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(tf[rt][k], v[k], acc[rt], 0, 0, 0);
+      for (int rt = 0; rt < RM; ++rt) acc[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(tf[rt][k], v[k], acc[rt], 0, 0, 0);
+      if constexpr (TAIL) fused_tail_fma(pt, tf[RT - 1][k], v[k]);
       es.slot(k);
       if constexpr (DEFER) post_slot(k, pmk, pso);
       __builtin_amdgcn_sched_barrier(0);
@@ -776,6 +838,9 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
       post_slot(KS, pmk, pso);
       __builtin_amdgcn_sched_barrier(0);                   // (the last store leaves here, not somewhere in the tail)
     }
+    double tail = 0.0;
+    if constexpr (TAIL) tail = fused_tail_scatter(pt);
+    (void)tail;
     FST(0);
     // (the alpha' row is USED here, unconditionally as far as the compiler can tell: its wait sits behind the MFMA loop)
 #pragma unroll
@@ -787,7 +852,7 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
     FST(1);
     double t = 0.0;
 #pragma unroll
-    for (int k = 0; k < KS; ++k) t += acc[k >> 2][k & 3];
+    for (int k = 0; k < KS; ++k) t += TEHMM_FUSED_PROD(k);
     t = item_sum4(t);
     const int e = ((__double2hiint(t) >> 20) & 0x7ff) - 1022;
     double bt[KS];
@@ -796,7 +861,7 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
     const double scale = okrow ? __hiloint2double((1023 - e) << 20, 0) : qnan;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-      bt[k] = acc[k >> 2][k & 3] * scale;                                  // beta_t
+      bt[k] = TEHMM_FUSED_PROD(k) * scale;                                             // beta_t
       if (s >= L && s == top) bt[k] = kq + 4 * k < N ? 1.0 : 0.0;           // uniform start
     }
     double g[KS];
@@ -917,5 +982,8 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
 #endif
 #undef FST
 }
+
+#undef TEHMM_FUSED_PROD
+#undef TEHMM_TAIL_FMA
 
 }  // namespace tehmm

@@ -1317,6 +1317,8 @@ struct EvalKnobs {
   int defer;            // TEHMM_DEFER: order of the posterior behind the Viterbi pipeline; -1: by batch size
   int gain_window;      // TEHMM_GAIN_WINDOW: positions of an item the gain pass runs on (0: all of them); -1: a quarter
   bool emis_fast;       // TEHMM_EMIS_FAST=0: the one-wave emission + gain kernel computes its rows with emis_rows everywhere
+  bool fused_tail;      // TEHMM_FUSED_TAIL=0: the fused posterior passes keep the padded row tile at 20 and 36 padded states
+  bool fused_tail_set;  // ... and whether it was set: the E-step reports count:fused_tail only then (its timing list is fixed)
   bool rowindex_ref;    // TEHMM_ROWINDEX_REF=1 (test-only): index records by k_fused_rowindex_ref, the layout's definition
   // 64 <= N <= 128
   bool wide;            // TEHMM_WIDE=0: the one-wave sequential kernels instead of the four-wave ones (k_*_wide)
@@ -1355,6 +1357,8 @@ static EvalKnobs read_eval_knobs() {
   k.defer = num("TEHMM_DEFER", -1);
   k.gain_window = std::getenv("TEHMM_GAIN_WINDOW") ? std::max(0, num("TEHMM_GAIN_WINDOW", 0)) : -1;
   k.emis_fast = num("TEHMM_EMIS_FAST", 1) != 0;
+  k.fused_tail = num("TEHMM_FUSED_TAIL", 1) != 0;
+  k.fused_tail_set = std::getenv("TEHMM_FUSED_TAIL") != nullptr;
   k.rowindex_ref = num("TEHMM_ROWINDEX_REF", 0) != 0;
   k.wide = num("TEHMM_WIDE", 1) != 0;
   k.wide_cp = num("TEHMM_WIDE_CP", 1) != 0;
@@ -2044,10 +2048,17 @@ static int fused_prepare(tehmm_batch *b, const tehmm_model *m, const IntervalTab
   return TEHMM_OK;
 }
 
+// Whether the fused passes of this model run in their tail form (tehmm_fused.hip.h: FusedTail, TEHMM_TAIL_FMA): the
+// knob, the linear-domain tables, 20 or 36 padded states.  What count:fused_tail reports.
+static bool fused_tail_runs(const tehmm_model *m, bool knob) {
+  return knob && fused_tail_nt(m->NP) && !m->ptab_log;
+}
+
 template <int NT>
 static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalTab &iv, const EmisTab &em_in,
-                           const FbChunks &fc, int Wu, hipStream_t st, hipEvent_t ev_fwd, hipEvent_t ev_mid,
+                           const FbChunks &fc, int Wu, hipStream_t st, hipEvent_t ev_fwd, hipEvent_t ev_mid, bool tail,
                            bool estep = false, int half = 0, hipEvent_t ev_fwdk = nullptr) {
+  // tail: fused_tail_runs of this model and call
   // half: 0 = the whole pipeline; 1 = the forward half only (pass, links, exact forward chain; ev_fwdk is recorded right
   // behind the pass itself), 2 = the backward half only -- tehmm_eval_batch puts the quantised Viterbi pass between them
   LaneWork &lw = b->lw;
@@ -2074,12 +2085,12 @@ static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalT
   const size_t lds_c = ((size_t)2 * 64 * (NT + 1) + 2 * 64 + NT + (size_t)emc.lds_rows * NT + 8) * sizeof(double);
   allow_lds(k_fb_fix<NT, 0, false, true, true>, lds_c);
   allow_lds(k_fb_fix<NT, 1, false, true, true>, lds_c);
-#define TEHMM_FUSED_LAUNCH(LOG_)                                                                                     \
+#define TEHMM_FUSED_LAUNCH(LOG_, TAIL_)                                                                                  \
   do {                                                                                                              \
-    allow_lds(k_fused_fwd<NT, LOG_>, lds_f);                                                                         \
-    allow_lds(k_fused_bwd<NT, LOG_, true>, lds_b);                                                                   \
+    allow_lds(k_fused_fwd<NT, LOG_, TAIL_>, lds_f);                                                                  \
+    allow_lds(k_fused_bwd<NT, LOG_, true, false, TAIL_>, lds_b);                                                     \
     if (half != 2) {                                                                                                \
-    hipLaunchKernelGGL((k_fused_fwd<NT, LOG_>), gridm, dim3(256), lds_f, st, iv, ft, lg, m->N, fc.CS, Wu,            \
+    hipLaunchKernelGGL((k_fused_fwd<NT, LOG_, TAIL_>), gridm, dim3(256), lds_f, st, iv, ft, lg, m->N, fc.CS, Wu,     \
                        (const double *)m->A.p, lw.AL32.p, lw.chkf.p, lw.pre_f.p, lw.end_f.p, lw.slog32.p);           \
     if (ev_fwdk) (void)hipEventRecord(ev_fwdk, st);                                                                  \
     hipLaunchKernelGGL((k_fb_itemlinks<NT>), gridit, dim3(256), 0, st, lg, m->N, lw.pre_f.p, lw.end_f.p,             \
@@ -2095,18 +2106,24 @@ static int launch_fused_fb(tehmm_batch *b, const tehmm_model *m, const IntervalT
     }                                                                                                               \
     if (half == 1) break;                                                                                           \
     if (estep) {                                                                                                    \
-      allow_lds(k_fused_bwd<NT, LOG_, false, true>, lds_f);                                                          \
-      hipLaunchKernelGGL((k_fused_bwd<NT, LOG_, false, true>), gridm, dim3(256), lds_f, st, iv, ft, lg, m->N, fc.CS, \
-                         Wu, (const double *)m->A.p, (const float *)lw.AL32.p, (double *)nullptr, lw.pre_b.p,        \
+      allow_lds(k_fused_bwd<NT, LOG_, false, true, TAIL_>, lds_f);                                                   \
+      hipLaunchKernelGGL((k_fused_bwd<NT, LOG_, false, true, TAIL_>), gridm, dim3(256), lds_f, st, iv, ft, lg, m->N, \
+                         fc.CS, Wu, (const double *)m->A.p, (const float *)lw.AL32.p, (double *)nullptr, lw.pre_b.p,        \
                          lw.end_b.p, lw.chk.p, lw.GAM32.p, lw.WZ32.p);                                               \
     } else {                                                                                                        \
-      hipLaunchKernelGGL((k_fused_bwd<NT, LOG_, true>), gridm, dim3(256), lds_b, st, iv, ft, lg, m->N, fc.CS,         \
-                         Wu, (const double *)m->A.p, (const float *)lw.AL32.p, b->post.p, lw.pre_b.p, lw.end_b.p,    \
+      hipLaunchKernelGGL((k_fused_bwd<NT, LOG_, true, false, TAIL_>), gridm, dim3(256), lds_b, st, iv, ft, lg, m->N, \
+                         fc.CS, Wu, (const double *)m->A.p, (const float *)lw.AL32.p, b->post.p, lw.pre_b.p, lw.end_b.p,    \
                          lw.chk.p, (float *)nullptr, (float *)nullptr, lw.sink.p);                                   \
     }                                                                                                               \
   } while (0)
-  if (m->ptab_log) TEHMM_FUSED_LAUNCH(true);
-  else TEHMM_FUSED_LAUNCH(false);
+  if (m->ptab_log) {
+    TEHMM_FUSED_LAUNCH(true, false);
+  } else if (tail) {
+    if constexpr (FusedTail<NT, false>::ok) TEHMM_FUSED_LAUNCH(false, true);
+    else return fail(TEHMM_ERR_ARG, "launch_fused_fb: no tail form at this state count");
+  } else {
+    TEHMM_FUSED_LAUNCH(false, false);
+  }
 #undef TEHMM_FUSED_LAUNCH
   if (half == 1) {
     HIPCHK(hipGetLastError());
@@ -2818,6 +2835,7 @@ struct EvalPlan {
   bool vspec;
   bool fspec;             // chunk-parallel forward / backward: N < 64, at least two chunks
   bool fused_fb;          // the fused posterior passes (tehmm_fused.hip.h): knob, the model's tables, K <= 78
+  bool fused_tail;        // ... in their tail form (fused_tail_runs)
   // item length of the lane = item passes (0: none).  Their item-interleaved buffers (8 * NP bytes per position each:
   // alpha' -- plus, without the fused passes, beta' and the linear emission rows --, the fp64 log rows of the exact
   // Viterbi pass; 4 * NP for the float rows of P0) must fit next to the results; otherwise the lane passes do without
@@ -2863,6 +2881,7 @@ static EvalPlan plan_eval(const tehmm_model *m, const tehmm_batch *b, int flags,
   p.vspec = p.vit && spec_ok && (!p.ratio || (ratio_lane_ok(m) && m->NP <= TEHMM_RATIO_LANE_MAX));
   p.fspec = p.postr && spec_ok;
   p.fused_fb = kn.fused && m->ptab.p != nullptr && m->K <= 78;        // (96 record entries incl. padding)
+  p.fused_tail = p.fused_fb && fused_tail_runs(m, kn.fused_tail);
   p.LS = (p.vspec || p.fspec) ? lane_sub_size(p.CS, b->total, kn.lane_sub) : 0;
   return p;
 }
@@ -3047,7 +3066,7 @@ static int eval_posterior(EvalCtx &c, int half) {
     }
     if (p.fused_fb) {
       nt_dispatch(m->NP, [&](auto nt) {
-        rc = launch_fused_fb<nt>(b, m, iv, c.em, fc, c.WuF, st, b->ev[eP + 3], b->ev[eP + 1], false, half,
+        rc = launch_fused_fb<nt>(b, m, iv, c.em, fc, c.WuF, st, b->ev[eP + 3], b->ev[eP + 1], p.fused_tail, false, half,
                                  half == 1 ? b->evX[1] : nullptr);
       });
       if (rc) return rc;
@@ -3414,6 +3433,7 @@ static int eval_counters(const EvalCtx &c) {
   auto add = [&](const char *name, double v) { add_counter(b, name, v); };
   if (c.p.fspec)
     if (int rc = add_chain_counters(b)) return rc;
+  if (c.p.flane && c.p.fused_fb) add("count:fused_tail", c.p.fused_tail ? 1 : 0);
   if (c.wide_cp) add("count:wide_chunk_parallel_warmup", b->ww.wu_ok);
   if (c.wide_vit) {
     int st2[2] = {0, 0};
