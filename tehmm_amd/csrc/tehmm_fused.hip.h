@@ -856,8 +856,13 @@ void k_fused_bwd(IntervalTab iv, FusedTab ft, LaneGeom lg, int N, int CS, int Wu
     t = item_sum4(t);
     const int e = ((__double2hiint(t) >> 20) & 0x7ff) - 1022;
     double bt[KS];
-    // an impossible emission row (all zeros) must poison the item: q enters v below, a zero v gives t = 0
-    const bool okrow = (s >= L && s >= top) || (t > 0.0 && t < INFINITY);
+    // An impossible emission row (all zeros) must poison the item: q enters v below, a zero v gives t = 0.  So must a
+    // product that underflowed without reaching 0: for a denormal t the exponent field is 0, the scale below 2^1022, and
+    // beta would be a row of ordinary size carrying only the few bits the denormal had left -- its later totals are normal
+    // numbers, its links hold, and the posteriors before the row are silently wrong (the E-step's wz = w * scale / G
+    // overflows on top of it).  Only a normal, finite total is a row computed here: exponent field 1 .. 2046, which is one
+    // unsigned test on the exponent e already at hand.
+    const bool okrow = (s >= L && s >= top) || (unsigned)(e + 1021) < 2046u;
     const double scale = okrow ? __hiloint2double((1023 - e) << 20, 0) : qnan;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {

@@ -355,7 +355,19 @@ __global__ __launch_bounds__(256) void k_fb_stitch(IntervalTab iv, LaneGeom lg, 
     if (okb) {
       for (int k = SUB - 2; k >= 0; --k) okb = okb && dl_b[item0 + k] <= TEHMM_FB_TOL;
       const double *w = end_b + (((item0 >> 6) * NT) << 6) + (item0 & 63);
-      for (int j = 0; j < NT; ++j) fc.wstart[(int64_t)c * NT + j] = j < N ? w[(int64_t)j << 6] : 0.0;
+      double wsum = 0.0;
+      for (int j = 0; j < NT; ++j) {
+        const double x = j < N ? w[(int64_t)j << 6] : 0.0;
+        fc.wstart[(int64_t)c * NT + j] = x;
+        wsum += x;
+      }
+      // wstart is the row a jump of the chain adopts at the chunk's first position.  Where the emission product of THAT
+      // position underflowed (a log-zero cell in every state, many peaked tracks) it is all zeros, or denormals with a
+      // few bits left, and nothing inside the chunk knows: k_fused_bwd meets it one step later, in the last item of the
+      // previous chunk, and the item's own links hold.  A chain that adopted zeros carried them to the interval's start:
+      // NaN posteriors and statistics from there on.  Such a chunk is walked exactly instead (its rows, from the log
+      // table, do not underflow).  The bound is the passes' own (k_fused_fwd, k_fused_bwd: okrow).
+      okb = okb && wsum > 1e-280 && wsum < INFINITY;
       // link to the next chunk (if the lanes ran it for the backward pass)
       if (okb && ct0 + 2 * (int64_t)fc.CS < T) lb = dl_b[item0 + SUB - 1] <= TEHMM_FB_TOL ? 1 : 0;
     }
