@@ -515,6 +515,50 @@ int tehmm_track_rows_won(int64_t T, int K, const int64_t *rec_offsets, const int
 int tehmm_load_tracks_f32(int64_t T, int K, const float *fill, const int64_t *rec_offsets, const int64_t *rec_start,
                           const int64_t *rec_end, const float *rec_val, float *out);
 
+/* ---- the per-row BED text of teHmmEval, formatted on the device (bin/teHmmEval.py:238-275) -----------
+ * Writes, for every table of a list, its optional header line (verbatim; headers or headers[t] NULL: none) and one line
+ * "chrom\tstart\tend\tX\n" per row, byte for byte what tehmm_bed_coords + tehmm_write_bed produce table by table.
+ * Table t owns rows row_offsets[t] .. row_offsets[t + 1] of the column (row_offsets [n_tables + 1], from 0, a table may
+ * be empty); segOffsets[t] [its rows] (NULL array or NULL entry: unsegmented), maskOffsets[t] [n_mask[t]] (NULL: none).
+ * kind: TEHMM_BED_NAMES X = names[states[r]] (0 to 1024 names of any length; a state outside them is TEHMM_ERR_ARG and
+ * the file is not touched), TEHMM_BED_INT X = states[r], TEHMM_BED_VALUE X = values[r] as tehmm_write_bed prints a
+ * float64.  shift: row i of a table carries the column entry of its row i - 1 and row 0 that of its last row (quirk Q15).
+ * The device formats every value whose rounding it can certify; the others (exact ties of the 12th digit and values
+ * within 2^-40 of one, subnormals, magnitudes beyond 1e-289 .. 1e281, NaN with the sign bit) get the host's snprintf.
+ * The work runs in stripes of stripe_rows items (rows and table headers; 0: 4 Mi), the copy-back of a stripe under the
+ * fwrite of the one before, through two pinned blocks of the tehmm_host_alloc pool. */
+#define TEHMM_BED_NAMES 0
+#define TEHMM_BED_INT 1
+#define TEHMM_BED_VALUE 2
+int tehmm_bed_text_write(const char *path, int append, int n_tables, const char *const *chroms, const int64_t *table_start,
+                         const int64_t *table_end, const int64_t *row_offsets, const int64_t *const *segOffsets,
+                         const int32_t *const *maskOffsets, const int64_t *n_mask, const char *const *headers, int kind,
+                         const int64_t *states, const double *values, int n_names, const char *const *names, int shift,
+                         int64_t stripe_rows);
+/* The same for tables that are the intervals interval0 .. interval0 + n_tables of a batch, the column taken from the
+ * device: the Viterbi path of the last evaluation, the maximum-posterior path of the last tehmm_batch_map_decode
+ * (names NULL: the integer state), the masked posterior sum (the column of tehmm_batch_posterior_masksum) or the masked
+ * emission column (that of tehmm_batch_emission_masksum; model and use_ratios as there).  The two value columns are
+ * computed inside the call and written with the one-row shift; no per-row column reaches the host.  TEHMM_ERR_ARG when
+ * the batch does not hold the evaluation a source needs. */
+#define TEHMM_BED_SRC_VITERBI 0
+#define TEHMM_BED_SRC_MAP 1
+#define TEHMM_BED_SRC_POSTERIOR 2
+#define TEHMM_BED_SRC_EMISSION 3
+int tehmm_batch_bed_text_write(tehmm_model_t *model, tehmm_batch_t *batch, int source, const double *mask, int use_ratios,
+                               int interval0, int n_tables, const char *const *chroms, const int64_t *table_start,
+                               const int64_t *table_end, const int64_t *const *segOffsets,
+                               const int32_t *const *maskOffsets, const int64_t *n_mask, const char *const *headers,
+                               int n_names, const char *const *names, const char *path, int append, int64_t stripe_rows);
+/* Of the calling thread's last call of the two above: rows and bytes written, rows the host formatted; and the device
+ * passes summed over the stripes ("measure", "scan", "patch", "emit"; "host": the null stream's idle time between
+ * stripes), then the host's "copy_wait", "fwrite" and "wall", as tehmm_segment_last_timing. */
+int tehmm_bed_text_last_counters(int64_t *rows, int64_t *bytes, int64_t *host_rows);
+int tehmm_bed_text_last_timing(int max_entries, const char **names, double *milliseconds);
+/* The value formatter of the two calls, run on the CPU (the same code the device runs; no GPU needed): text [24] gets
+ * the characters of x, *certified = 1 when the device path certified its rounding, 0 when the text is the host's. */
+int tehmm_bed_text_format_value(double x, char *text, int *certified);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

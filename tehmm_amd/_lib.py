@@ -98,6 +98,17 @@ SIGNATURES = {
     "tehmm_bed_coords": (c_int, [c_i64, c_i64, c_i64, i64p, i32p, c_i64, i64p, i64p]),
     "tehmm_write_bed": (c_int, [ctypes.c_char_p, c_int, ctypes.c_char_p, c_i64, i64p, i64p, i64p, c_int,
                                 ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_bed_text_write": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.POINTER(ctypes.c_char_p), i64p, i64p, i64p,
+                                     ctypes.POINTER(i64p), ctypes.POINTER(i32p), i64p,
+                                     ctypes.POINTER(ctypes.c_char_p), c_int, i64p, f64p, c_int,
+                                     ctypes.POINTER(ctypes.c_char_p), c_int, c_i64]),
+    "tehmm_batch_bed_text_write": (c_int, [vp, vp, c_int, f64p, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_char_p),
+                                           i64p, i64p, ctypes.POINTER(i64p), ctypes.POINTER(i32p), i64p,
+                                           ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(ctypes.c_char_p),
+                                           ctypes.c_char_p, c_int, c_i64]),
+    "tehmm_bed_text_format_value": (c_int, [c_dbl, ctypes.c_char_p, ctypes.POINTER(c_int)]),
+    "tehmm_bed_text_last_counters": (c_int, [i64p, i64p, i64p]),
+    "tehmm_bed_text_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_model_create": (c_int, [c_int, c_int, c_int, f64p, f64p, f64p, c_dbl, i32p,
                                    ctypes.POINTER(vp)]),
     "tehmm_model_destroy": (c_int, [vp]),

@@ -20,9 +20,11 @@
 #include "tehmm_masking.hip.h"
 #include "tehmm_trackio.hip.h"
 #include "tehmm_scaling.hip.h"
+#include "tehmm_bedtext.hip.h"
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -3887,10 +3889,11 @@ void launch_edist(bool col, dim3 grid, hipStream_t st, const IntervalTab &iv, co
   else hipLaunchKernelGGL((k_edist<W, SPL, false>), grid, dim3(256), 0, st, iv, em, N, row0, row1, first, mask, out);
 }
 
-// mask != NULL: the column; else the frame.  dst is a host buffer.
+// mask != NULL: the column; else the frame.  dst is a host buffer; dev_col (column only): the column stays on the device,
+// *dev_col [row1 - row0] is valid until the batch's next emission call
 int emission_dist(tehmm_model *m, tehmm_batch *b, int use_ratios, const double *mask, bool col, int64_t row0, int64_t row1,
-                  double *dst, const char *who) {
-  if (!m || !b || !dst || (col && !mask)) return fail(TEHMM_ERR_ARG, std::string(who) + ": NULL argument");
+                  double *dst, const char *who, double **dev_col = nullptr) {
+  if (!m || !b || (!dst && !(col && dev_col)) || (col && !mask)) return fail(TEHMM_ERR_ARG, std::string(who) + ": NULL argument");
   if (m->N > TEHMM_LARGE_MAX) return fail(TEHMM_ERR_UNSUPPORTED, std::string(who) + ": N > 1024");
   if (m->K != b->K) return fail(TEHMM_ERR_ARG, std::string(who) + ": model/batch track count differ");
   if (row0 < 0 || row1 < row0 || row1 > b->total) return fail(TEHMM_ERR_ARG, std::string(who) + ": bad row range");
@@ -3945,6 +3948,10 @@ int emission_dist(tehmm_model *m, tehmm_batch *b, int use_ratios, const double *
   (void)hipEventElapsedTime(&ms, b->ev[13], b->ev[14]);
   b->tnames.push_back(name);
   b->tms.push_back((double)ms);
+  if (col && dev_col) {
+    *dev_col = d_out;
+    return TEHMM_OK;
+  }
   const int rc = d2h(dst, d_out, (size_t)rows * (col ? 1 : N) * sizeof(double), b);
   if (!col && b->sP) (void)hipStreamSynchronize(b->sP);      // (the staged copy read the frame block on that stream)
   return rc;
@@ -4190,6 +4197,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
 #include "tehmm_masking_host.inc"
 #include "tehmm_trackio_host.inc"
 #include "tehmm_scaling_host.inc"
+#include "tehmm_bedtext_host.inc"
 
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {

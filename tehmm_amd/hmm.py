@@ -186,6 +186,94 @@ class MultitrackHmm(BaseHMM):
             hb.close()
         return out
 
+    def evalToFiles(self, trackData, bedPath=None, pdPath=None, pdMask=None, edPath=None, edMask=None, maxPost=False,
+                    append=False, stripeRows=0):
+        """What the table loop of teHmmEval writes (teHmmEval.py:171-204), from ONE evaluation per batch and with the
+        lines formatted on the device (output.writeBatchBed): the states file with a "#Viterbi Score" line before every
+        table, the --pd file (masked posterior sums) and the --ed file (masked emission column).  The decoding is
+        viterbi() or, with maxPost, posteriorDecode() -- maximum-posterior states only for a model built with
+        algorithm "map" (quirk Q14).  Tables with and without segment ratios go to two batches, as in _eval_tables and
+        _emission_tables, and the files still hold the tables in TrackData order.  Tables that cannot fuse take the
+        array-level calls and output.writeBedText.  Returns (scores, forward log-probabilities or None), per table."""
+        from . import output
+        tables = trackData.getTrackTableList()
+        n = len(tables)
+        use_map = self._algorithm == "map"
+        want_pd = pdPath is not None and bedPath is not None
+        want_ed = edPath is not None and bedPath is not None
+        names = None
+        if self.stateNameMap is not None:
+            names = [str(self.stateNameMap.getMapBack(i)) for i in range(self.n_components)]
+        paths = [p for p, want in ((bedPath, True), (pdPath, want_pd), (edPath, want_ed)) if p is not None and want]
+        if not append:
+            for p in paths:
+                open(p, "w").close()
+        if n == 0:
+            return [], None
+        if not self._can_fuse(tables):
+            decoded = self.posteriorDecode(trackData) if maxPost else self.viterbi(trackData)
+            scores = [d[0] for d in decoded]
+            if bedPath is not None:
+                heads = ["#Viterbi Score: %f\n" % s for s in scores]
+                res = self._eval_tables(tables, viterbi=not use_map, posterior=False, map_decode=use_map)
+                states = np.concatenate(res["map_paths"] if use_map else res["paths"])
+                output.writeBedText(bedPath, tables, states=states, names=names, headers=heads, append=True,
+                                    stripeRows=stripeRows)
+            if want_pd:
+                post = self.posteriorDistribution(trackData)
+                col = np.concatenate([np.sum(p * pdMask, axis=1) for p in post])
+                output.writeBedText(pdPath, tables, values=col, shift=True, append=True, stripeRows=stripeRows)
+            if want_ed:
+                col = np.concatenate(self.emissionColumn(trackData, edMask))
+                output.writeBedText(edPath, tables, values=col, shift=True, append=True, stripeRows=stripeRows)
+            return scores, None
+        from .engine import HipBatch
+        arrays = [t.getNumPyArray() if isinstance(t, TrackTable) else np.ascontiguousarray(t) for t in tables]
+        ratios = [self.emissionModel.getSegmentRatios(t) for t in tables]
+        hm = self._device_model()
+        scores, fwd = [None] * n, [None] * n
+        group_of, slot_of, batches = [0] * n, [0] * n, {}
+        try:
+            for has_r in (True, False):
+                idx = [i for i, r in enumerate(ratios) if (r is not None) == has_r]
+                if not idx:
+                    continue
+                lens = np.asarray([arrays[i].shape[0] for i in idx], dtype=np.int64)
+                offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+                obs = np.concatenate([arrays[i] for i in idx], axis=0)
+                hb = HipBatch(obs, offs, np.concatenate([ratios[i] for i in idx]) if has_r else None)
+                batches[has_r] = hb
+                res = hm.eval(hb, viterbi=not use_map, posterior=want_pd, use_ratios=has_r and not use_map,
+                              map_decode=use_map)
+                for k, i in enumerate(idx):
+                    group_of[i], slot_of[i] = has_r, k
+                    scores[i] = (res["map_logprob"] if use_map else res["viterbi_logprob"])[k]
+                    if res["forward_logprob"] is not None:
+                        fwd[i] = res["forward_logprob"][k]
+            if use_map:
+                for lp in fwd:
+                    self._note_forward_logprob(lp)
+            # runs of neighbouring tables of one batch: one call each, in TrackData order
+            i = 0
+            while i < n and bedPath is not None:
+                j = i
+                while j + 1 < n and group_of[j + 1] == group_of[i] and slot_of[j + 1] == slot_of[j] + 1:
+                    j += 1
+                hb, run = batches[group_of[i]], tables[i:j + 1]
+                common = dict(interval0=slot_of[i], append=True, stripeRows=stripeRows)
+                output.writeBatchBed(bedPath, hb, output.SRC_MAP if use_map else output.SRC_VITERBI, run, names=names,
+                                     headers=["#Viterbi Score: %f\n" % scores[k] for k in range(i, j + 1)], **common)
+                if want_pd:
+                    output.writeBatchBed(pdPath, hb, output.SRC_POSTERIOR, run, mask=pdMask, **common)
+                if want_ed:
+                    output.writeBatchBed(edPath, hb, output.SRC_EMISSION, run, model=hm, mask=edMask,
+                                         useRatios=group_of[i], **common)
+                i = j + 1
+        finally:
+            for hb in batches.values():
+                hb.close()
+        return scores, (fwd if any(x is not None for x in fwd) else None)
+
     def getTrackList(self):
         return self.trackList
 

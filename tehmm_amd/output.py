@@ -57,6 +57,118 @@ def statesToBed(trackTable, states, bedPath=None, posteriorSums=None, posteriors
         _write(emissionsPath, append, chrom, starts, ends, values=np.roll(np.asarray(emissionSums), 1))
 
 
+# ---- the same lines formatted on the device (tehmm_bed_text_write) -------------------------------------
+KIND_NAMES, KIND_INT, KIND_VALUE = 0, 1, 2
+SRC_VITERBI, SRC_MAP, SRC_POSTERIOR, SRC_EMISSION = 0, 1, 2, 3
+_cpp = ctypes.POINTER(ctypes.c_char_p)
+
+
+def _describe(table):
+    """(chrom, start, end, rows, segOffsets, maskOffsets) of a TrackTable, or such a tuple itself"""
+    if isinstance(table, (tuple, list)):
+        chrom, start, end, rows, seg, mo = table
+    else:
+        chrom, start, end, rows = table.getChrom(), table.getStart(), table.getEnd(), len(table)
+        seg = table.getSegmentOffsets()
+        mo = table.getMaskRunningOffsets() if hasattr(table, "getMaskRunningOffsets") else None
+    seg = None if seg is None else np.ascontiguousarray(seg, dtype=np.int64)
+    mo = None if mo is None else np.ascontiguousarray(mo, dtype=np.int32)
+    if seg is not None and len(seg) != rows:
+        raise ValueError("segOffsets holds %d entries for a table of %d rows" % (len(seg), rows))
+    return str(chrom).encode(), int(start), int(end), int(rows), seg, mo
+
+
+def _strings(items):
+    return None if items is None else (ctypes.c_char_p * len(items))(
+        *[None if x is None else (x if isinstance(x, bytes) else str(x).encode()) for x in items])
+
+
+class _TableArgs(object):
+    """The per-table arrays of the two calls (and the numpy arrays behind their pointers)."""
+
+    def __init__(self, tables, headers):
+        d = [_describe(t) for t in tables]
+        n = self.n = len(d)
+        if headers is not None and len(headers) != n:
+            raise ValueError("one header (or None) per table")
+        self.chroms = _strings([x[0] for x in d])
+        self.start = np.asarray([x[1] for x in d], dtype=np.int64)
+        self.end = np.asarray([x[2] for x in d], dtype=np.int64)
+        self.row_offsets = np.concatenate([[0], np.cumsum([x[3] for x in d])]).astype(np.int64)
+        self.keep = [(x[4], x[5]) for x in d]
+        self.seg = self.mask = None
+        if any(x[4] is not None for x in d):
+            self.seg = (i64p * n)(*[i64p() if x[4] is None else ptr(x[4], i64p) for x in d])
+        if any(x[5] is not None for x in d):
+            self.mask = (i32p * n)(*[i32p() if x[5] is None else ptr(x[5], i32p) for x in d])
+        self.n_mask = np.asarray([0 if x[5] is None else len(x[5]) for x in d], dtype=np.int64)
+        self.headers = _strings(headers)
+
+
+def writeBedText(path, tables, states=None, values=None, names=None, headers=None, shift=False, append=False,
+                 stripeRows=0):
+    """The lines of a list of tables, formatted on the device: the bytes bedCoords + tehmm_write_bed produce table by
+    table.  tables: TrackTables, or tuples (chrom, start, end, rows, segOffsets or None, maskOffsets or None);
+    states (int, with names: names[state], else the integer) or values (float64) is the concatenated column of all
+    tables; headers: per table a line written verbatim before its rows, or None.  shift: quirk Q15, per table."""
+    a = _TableArgs(tables, headers)
+    rows = int(a.row_offsets[-1])
+    st = vals = None
+    if values is not None:
+        kind = KIND_VALUE
+        vals = np.ascontiguousarray(values, dtype=np.float64)
+        assert vals.shape == (rows,)
+    else:
+        kind = KIND_INT if names is None else KIND_NAMES
+        st = np.ascontiguousarray(states, dtype=np.int64)
+        assert st.shape == (rows,)
+    nm = _strings(None if names is None else list(names))
+    _lib.check(_lib.load().tehmm_bed_text_write(
+        str(path).encode(), 1 if append else 0, a.n, a.chroms, ptr(a.start, i64p), ptr(a.end, i64p),
+        ptr(a.row_offsets, i64p), a.seg, a.mask, ptr(a.n_mask, i64p), a.headers, kind, ptr(st, i64p), ptr(vals, f64p),
+        0 if names is None else len(names), nm, 1 if shift else 0, int(stripeRows)), "tehmm_bed_text_write")
+
+
+def writeBatchBed(path, batch, source, tables, model=None, mask=None, useRatios=False, interval0=0, names=None,
+                  headers=None, append=False, stripeRows=0):
+    """The same over intervals interval0 .. interval0 + len(tables) of a HipBatch, the column read or computed on the
+    device: SRC_VITERBI / SRC_MAP (the state, names[state] with names), SRC_POSTERIOR (the masked posterior sum) or
+    SRC_EMISSION (the masked emission column of `model`, a HipModel); the two value columns come with the one-row
+    shift of quirk Q15.  No per-row column reaches the host."""
+    a = _TableArgs(tables, headers)
+    offs = np.asarray(batch.offsets[int(interval0):int(interval0) + a.n + 1], dtype=np.int64)
+    if len(offs) != a.n + 1 or not np.array_equal(offs - offs[0], a.row_offsets):
+        raise ValueError("the tables are not intervals %d .. %d of the batch" % (interval0, interval0 + a.n))
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+    if mk is not None and source in (SRC_POSTERIOR, SRC_EMISSION):
+        n_states = batch.N if source == SRC_POSTERIOR or model is None else model.N
+        if n_states is not None and mk.shape != (n_states,):
+            raise ValueError("the mask needs one entry per state")
+    nm = _strings(None if names is None else list(names))
+    _lib.check(_lib.load().tehmm_batch_bed_text_write(
+        None if model is None else model._h, batch._h, int(source), ptr(mk, f64p), 1 if useRatios else 0,
+        int(interval0), a.n, a.chroms, ptr(a.start, i64p), ptr(a.end, i64p), a.seg, a.mask, ptr(a.n_mask, i64p),
+        a.headers, 0 if names is None else len(names), nm, str(path).encode(), 1 if append else 0, int(stripeRows)),
+        "tehmm_batch_bed_text_write")
+
+
+def lastBedTextCounters():
+    """(rows, bytes, rows the host formatted) of this thread's last writeBedText / writeBatchBed"""
+    r, b, h = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().tehmm_bed_text_last_counters(ctypes.byref(r), ctypes.byref(b), ctypes.byref(h)),
+               "tehmm_bed_text_last_counters")
+    return r.value, b.value, h.value
+
+
+def lastBedTextTiming():
+    """[(pass, milliseconds)] of this thread's last writeBedText / writeBatchBed"""
+    names = (ctypes.c_char_p * 16)()
+    ms = (ctypes.c_double * 16)()
+    n = _lib.load().tehmm_bed_text_last_timing(16, names, ms)
+    _lib.check(min(n, 0), "tehmm_bed_text_last_timing")
+    return [(names[i].decode(), ms[i]) for i in range(n)]
+
+
 def getPosteriorsMask(pdStates, model):
     """teHmmEval.py:294-311: mask[i] == 1 iff state i is named in the comma-separated `pdStates` (--pdStates and
     --edStates); the states of a model without a state-name map are named "0", "1", ...  A name the model does not
