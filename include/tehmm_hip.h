@@ -559,6 +559,31 @@ int tehmm_bed_text_last_timing(int max_entries, const char **names, double *mill
  * the characters of x, *certified = 1 when the device path certified its rounding, 0 when the text is the host's. */
 int tehmm_bed_text_format_value(double x, char *text, int *certified);
 
+/* ---- CYK decode of the grammar model (cfg.py:219-304, _cfg.pyx:16-89) ---------------------------------
+ * Decodes a batch of intervals; all arrays are host pointers.  Interval t owns rows offsets[t] .. offsets[t + 1]
+ * (offsets [n + 1], from 0, every interval at least one row) of emLogProbs [total][M] (the rows of allLogProbs), of
+ * alignment [total] (NULL: no alignment track) and of trace.  is_nest [M] marks the pair states; logProbs1 [M][M][M]
+ * and logProbs2 [M][M] are the reference's tables (every entry above -inf is a production, -1e100 included),
+ * logPriors [M][2] is indexed [state][match], log_start [M].
+ * Results: scores[t] = max over x of log_start[x] + dp[0][L-1][x], top[t] its first arg-max, trace [total] the state of
+ * every row as float64 (the reference's array).  Scores, states and every dp cell equal the reference's bit for bit:
+ * the additions run in its order, ties go to the candidate its scan meets first.
+ * TEHMM_ERR_UNSUPPORTED before any allocation for M > 64 and for intervals whose workspace does not fit the device
+ * (the message names the largest L that fits); TEHMM_ERR_ARG, after the results were copied, when a derivation reaches
+ * a cell that no production fills (the reference's assertion).  Additions to ABI version 4: detect them by symbol. */
+int tehmm_cyk_decode(int n_intervals, const int64_t *offsets, int M, const double *emLogProbs, const uint16_t *alignment,
+                     int defAlignmentSymbol, const uint8_t *is_nest, const double *logProbs1, const double *logProbs2,
+                     const double *logPriors, const double *log_start, double *scores, int64_t *top, double *trace);
+/* Test accessor: the full table dp [L][L][M] of one interval, -inf below the diagonal as the reference leaves it. */
+int tehmm_cyk_get_dp(int64_t L, int M, const double *emLogProbs, const uint16_t *alignment, int defAlignmentSymbol,
+                     const uint8_t *is_nest, const double *logProbs1, const double *logProbs2, const double *logPriors,
+                     const double *log_start, double *dp);
+/* Device time of the passes of the calling thread's last call of the two above ("upload", "init", "fill",
+ * "traceback", "copy_back"), then the host's "wall", as tehmm_segment_last_timing. */
+int tehmm_cyk_last_timing(int max_entries, const char **names, double *milliseconds);
+/* Bytes of device memory a decode of intervals of these lengths takes (no device call). */
+int64_t tehmm_cyk_workspace_bytes(int n_intervals, const int64_t *lengths, int M);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

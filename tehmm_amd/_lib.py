@@ -15,6 +15,7 @@ f32p = ctypes.POINTER(ctypes.c_float)
 i64p = ctypes.POINTER(ctypes.c_int64)
 i32p = ctypes.POINTER(ctypes.c_int32)
 u8p = ctypes.POINTER(ctypes.c_uint8)
+u16p = ctypes.POINTER(ctypes.c_uint16)
 vp = ctypes.c_void_p
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -109,6 +110,10 @@ SIGNATURES = {
     "tehmm_bed_text_format_value": (c_int, [c_dbl, ctypes.c_char_p, ctypes.POINTER(c_int)]),
     "tehmm_bed_text_last_counters": (c_int, [i64p, i64p, i64p]),
     "tehmm_bed_text_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_cyk_decode": (c_int, [c_int, i64p, c_int, f64p, u16p, c_int, u8p, f64p, f64p, f64p, f64p, f64p, i64p, f64p]),
+    "tehmm_cyk_get_dp": (c_int, [c_i64, c_int, f64p, u16p, c_int, u8p, f64p, f64p, f64p, f64p, f64p]),
+    "tehmm_cyk_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_cyk_workspace_bytes": (c_i64, [c_int, i64p, c_int]),
     "tehmm_model_create": (c_int, [c_int, c_int, c_int, f64p, f64p, f64p, c_dbl, i32p,
                                    ctypes.POINTER(vp)]),
     "tehmm_model_destroy": (c_int, [vp]),

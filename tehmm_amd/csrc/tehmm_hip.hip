@@ -21,6 +21,7 @@
 #include "tehmm_trackio.hip.h"
 #include "tehmm_scaling.hip.h"
 #include "tehmm_bedtext.hip.h"
+#include "tehmm_cyk.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4198,6 +4199,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
 #include "tehmm_trackio_host.inc"
 #include "tehmm_scaling_host.inc"
 #include "tehmm_bedtext_host.inc"
+#include "tehmm_cyk_host.inc"
 
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {

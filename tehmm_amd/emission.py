@@ -391,3 +391,28 @@ class IndependentMultinomialAndGaussianEmissionModel(IndependentMultinomialEmiss
         self.gaussParams[track.getNumber(), state, 1] = float(toks[3])
         self.applyGaussian(track, state, logProbs)
         mask[track.getNumber(), state, :] = 1
+
+
+class PairEmissionModel(object):
+    """emission.py:621-650: the emission of a pair of columns by one state is the product of the two single
+    emissions and a prior on whether the alignment track links the two columns.  pairPriors holds, per state, the
+    confidence p in a link: logPriors[state] = [log(1 - p), log p], indexed by match; None: no prior at all."""
+
+    def __init__(self, emissionModel, pairPriors):
+        self.em = emissionModel
+        pp = []
+        for p in pairPriors:
+            if p is None:
+                pp.append([0, 0])
+            elif p == 1:
+                pp.append([-np.inf, 0.])
+            else:
+                with np.errstate(divide="ignore"):
+                    pp.append([np.log(1. - p), np.log(p)])
+        self.logPriors = np.array(pp, dtype=np.float64).reshape(len(pp), 2)
+        assert self.logPriors.shape == (self.em.getNumStates(), 2)
+
+    def pairLogProb(self, state, logProb1, logProb2, match):
+        assert match == 0 or match == 1
+        assert state < len(self.logPriors)
+        return logProb1 + logProb2 + self.logPriors[state, int(match)]

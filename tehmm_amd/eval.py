@@ -1,5 +1,6 @@
-"""teHmmEval -- the reference's bin/teHmmEval.py for MultitrackHmm models (the CFG branch is not offered): decode a data
-set with a trained model, print its score and optionally write the per-row files.
+"""teHmmEval -- the reference's bin/teHmmEval.py: decode a data set with a trained model, print its score and
+optionally write the per-row files.  A MultitrackCfg model is decoded by CYK on the device (cfgEval: --bed and --bic;
+--slice bounds the cubic work; --maxPost, --pd, --ed and --segment are refused before data is loaded).
 
 Same positionals, options, defaults and errors as the reference (teHmmEval.py:25-105).  Tracks are loaded through
 TrackData.loadTrackData, the model is read by modelIO, every table of a run is evaluated in one fused launch per ratio
@@ -119,10 +120,20 @@ def chromJobs(regions, chromIntervals, intersect=None):
 def runEval(args, out=None):
     """One run of the tool on args.bedRegions (teHmmEval.py:113-236)."""
     from . import modelIO, trackIO
+    from .cfg import MultitrackCfg
     from .track import TrackData
     out = sys.stdout if out is None else out
     logger.info("loading model %s" % args.inputModel)
     model = modelIO.loadModel(args.inputModel)
+    isCfg = isinstance(model, MultitrackCfg)
+    if isCfg:
+        # teHmmEval.py:117-119; the grammar model has no posterior or emission column either
+        if args.maxPost is True:
+            raise RuntimeError("--maxPost not supported on CFG models")
+        if args.pd is not None or args.ed is not None:
+            raise RuntimeError("--pd and --ed not supported on CFG models")
+        if args.segment is True:
+            raise RuntimeError("--segment not supported on CFG models")
 
     if args.segLen > 0:
         assert args.segment is True
@@ -141,7 +152,10 @@ def runEval(args, out=None):
 
     logger.info("loading tracks %s" % args.tracksInfo)
     trackData = TrackData()
-    trackData.loadTrackData(args.tracksInfo, choppedIntervals, model.getTrackList(), segmentIntervals=segIntervals)
+    trackData.loadTrackData(args.tracksInfo, choppedIntervals, model.getTrackList(), segmentIntervals=segIntervals,
+                            allowAlignment=isCfg)
+    if isCfg:
+        return cfgEval(args, model, trackData, out)
 
     logger.info("running %s algorithm" % ("posterior decoding" if args.maxPost is True else "viterbi"))
     pdMask = edMask = None
@@ -163,6 +177,34 @@ def runEval(args, out=None):
     out.write("Viterbi (log) score: %f\n" % totalScore)
     if getattr(model, "current_iteration", None) is not None:
         out.write("Number of EM iterations: %d\n" % model.current_iteration)
+    if args.bic is not None:
+        writeBic(args.bic, model, totalScore, totalDatapoints)
+    return 0
+
+
+def cfgEval(args, model, trackData, out):
+    """The CFG branch of teHmmEval.py:158-236: CYK over all tables in one device call, the --bed file through the
+    writers of the HMM branch with the trace as the state rows.  The work grows with the cube of an interval's
+    length: --slice bounds it."""
+    from .output import statesToBed
+    logger.info("running CYK algorithm")
+    if args.bed is not None:
+        open(args.bed, "w").close()
+    totalScore = 0
+    totalDatapoints = 0
+    names = None
+    if model.getStateNameMap() is not None:
+        names = [model.getStateNameMap().getMapBack(i) for i in range(model.getEmissionModel().getNumStates())]
+    for table, (score, states) in zip(trackData.getTrackTableList(), model.viterbi(trackData)):
+        totalScore += score
+        if args.bed is not None:
+            with open(args.bed, "a") as f:
+                f.write("#Viterbi Score: %f\n" % score)
+            if names is not None:
+                states = [model.getStateNameMap().getMap(s) for s in states]
+            statesToBed(table, [int(s) for s in states], args.bed, stateNames=names)
+            totalDatapoints += len(table) * table.getNumTracks()
+    out.write("Viterbi (log) score: %f\n" % totalScore)
     if args.bic is not None:
         writeBic(args.bic, model, totalScore, totalDatapoints)
     return 0

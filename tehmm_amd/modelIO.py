@@ -10,6 +10,7 @@ import numpy as np
 
 FORMAT = "tehmm_amd.model.v2"
 FORMAT_V1 = "tehmm_amd.model.v1"       # round-2 files: arrays only (no track list, value maps, flags)
+KIND_HMM, KIND_CFG = "hmm", "cfg"      # the `kind` array of a v2 file (files from before it had one: an HMM)
 
 
 def _load_v1(z):
@@ -34,9 +35,13 @@ def _load_v1(z):
 
 
 def _map_to_json(vm):
-    from .track import CategoryMap, IdentityValueMap
+    from .track import BinaryMap, CategoryMap, IdentityValueMap
     if vm is None:
         return None
+    if isinstance(vm, BinaryMap):
+        # (written as a category map it came back as one without entries: every row of a binary track then read as
+        # missing data in teHmmEval.  Files from before this type still load that way.)
+        return {"type": "binary"}
     if isinstance(vm, IdentityValueMap):
         return {"type": "identity", "scale": vm.scale, "shift": vm.shift}
     if isinstance(vm, CategoryMap):
@@ -51,9 +56,11 @@ def _map_to_json(vm):
 
 def _map_from_json(d):
     import ast
-    from .track import CategoryMap, IdentityValueMap
+    from .track import BinaryMap, CategoryMap, IdentityValueMap
     if d is None:
         return None
+    if d["type"] == "binary":
+        return BinaryMap()
     if d["type"] == "identity":
         return IdentityValueMap(d["scale"], d["shift"])
 
@@ -68,20 +75,58 @@ def _map_from_json(d):
     return vm
 
 
-def saveModel(path, hmm):
+def _track_to_json(t):
+    return {"name": t.getName(), "number": int(t.getNumber()), "dist": t.getDist(),
+            "valueMap": _map_to_json(t.getValueMap())}
+
+
+def _common_meta(model):
+    """What both model classes store beside their arrays: the emission model's flags, the track list, the state names."""
     from .emission import IndependentMultinomialAndGaussianEmissionModel
-    hmm.validate()
-    em = hmm.getEmissionModel()
-    gp = getattr(em, "gaussParams", None)
-    tl = hmm.getTrackList()
-    meta = {
+    em = model.getEmissionModel()
+    tl = model.getTrackList()
+    return {
         "emission_class": "gaussian" if isinstance(em, IndependentMultinomialAndGaussianEmissionModel) else "multinomial",
         "zeroAsMissingData": bool(em.zeroAsMissingData),
         "uniformMixProb": float(em.uniformMixProb),
         "randRange": list(em.randRange),
-        "tracks": None if tl is None else [{"name": t.getName(), "number": int(t.getNumber()), "dist": t.getDist(),
-                                            "valueMap": _map_to_json(t.getValueMap())} for t in tl],
-        "stateNameMap": _map_to_json(hmm.getStateNameMap()),
+        "tracks": None if tl is None else [_track_to_json(t) for t in tl],
+        "stateNameMap": _map_to_json(model.getStateNameMap()),
+    }
+
+
+def _emission_arrays(em):
+    gp = getattr(em, "gaussParams", None)
+    return dict(log_probs=em.getLogProbs(), symbols=np.asarray(em.getNumSymbolsPerTrack(), dtype=np.int64),
+                normalize_fac=float(em.normalizeFac), fudge=float(em.fudge),
+                eff_seg_len=np.asarray(-1.0 if em.effectiveSegmentLength is None else em.effectiveSegmentLength),
+                gauss_params=np.zeros(0) if gp is None else gp)
+
+
+def _save_cfg(path, cfg):
+    """A MultitrackCfg: both production tables, start probabilities, pair states and logPriors next to the emission
+    model; the alignment track travels with the track list."""
+    cfg.validate()
+    meta = _common_meta(cfg)
+    tl = cfg.getTrackList()
+    al = None if tl is None else tl.getAlignmentTrack()
+    meta["alignmentTrack"] = None if al is None else _track_to_json(al)
+    with open(path, "wb") as f:
+        np.savez(f, format=np.asarray(FORMAT), kind=np.asarray(KIND_CFG), log_probs1=cfg.logProbs1,
+                 log_probs2=cfg.logProbs2, log_startprob=cfg.startProbs,
+                 nest_states=np.asarray(cfg.nestStates, dtype=np.int64),
+                 log_priors=np.asarray(cfg.pairEmissionModel.logPriors, dtype=np.float64),
+                 meta=np.asarray(json.dumps(meta)), **_emission_arrays(cfg.getEmissionModel()))
+
+
+def saveModel(path, hmm):
+    from .cfg import MultitrackCfg
+    if isinstance(hmm, MultitrackCfg):
+        return _save_cfg(path, hmm)
+    hmm.validate()
+    em = hmm.getEmissionModel()
+    meta = _common_meta(hmm)
+    meta.update({
         "hmm": {"fudge": float(hmm.fudge), "fixTrans": bool(hmm.fixTrans), "fixEmission": bool(hmm.fixEmission),
                 "fixStart": bool(hmm.fixStart), "maxProb": bool(hmm.maxProb),
                 "maxProbCut": hmm.maxProbCut, "transMatEpsilons": bool(hmm.transMatEpsilons),
@@ -89,21 +134,16 @@ def saveModel(path, hmm):
                 "numZeroInitEdges": int(hmm.numZeroInitEdges), "numZeroInitStarts": int(hmm.numZeroInitStarts),
                 "last_forward_log_prob": hmm.last_forward_log_prob,
                 "last_forward_log_prob_it": int(hmm.last_forward_log_prob_it)},
-    }
+    })
     force = {"trans": hmm.forceUserTrans, "emissions": hmm.forceUserEmissions, "start": hmm.forceUserStart}
     if any(v is not None for v in force.values()):
         # (optional key: the force line lists travel with the model, as they do in the reference's pickle)
         meta["forceUser"] = {k: None if v is None else [str(x) for x in v] for k, v in force.items()}
     with open(path, "wb") as f:
-        np.savez(f, format=np.asarray(FORMAT), log_transmat=hmm._log_transmat,
+        np.savez(f, format=np.asarray(FORMAT), kind=np.asarray(KIND_HMM), log_transmat=hmm._log_transmat,
                  log_startprob=hmm._log_startprob,
-                 log_probs=em.getLogProbs(),
-                 symbols=np.asarray(em.getNumSymbolsPerTrack(), dtype=np.int64),
-                 normalize_fac=float(em.normalizeFac), fudge=float(em.fudge),
-                 eff_seg_len=np.asarray(-1.0 if em.effectiveSegmentLength is None else em.effectiveSegmentLength),
-                 gauss_params=np.zeros(0) if gp is None else gp,
                  iteration=np.asarray(-1 if hmm.current_iteration is None else hmm.current_iteration),
-                 meta=np.asarray(json.dumps(meta)))
+                 meta=np.asarray(json.dumps(meta)), **_emission_arrays(em))
 
 
 def loadModel(path):
@@ -120,10 +160,17 @@ def loadModel(path):
         lp = z["log_probs"]
         eff = float(z["eff_seg_len"])
         symbols = [int(x) for x in z["symbols"]]
+        kind = str(z["kind"]) if "kind" in z.files else KIND_HMM
+        if kind not in (KIND_HMM, KIND_CFG):
+            raise ValueError("loadModel: %s holds a model of unknown kind %r" % (path, kind))
         tl = None
         if meta["tracks"] is not None:
             tl = TrackList(Track(t["name"], t["number"], t["dist"], _map_from_json(t["valueMap"]))
                            for t in meta["tracks"])
+            al = meta.get("alignmentTrack")
+            if al is not None:
+                tl.addTrack(Track(al["name"], al["number"], al["dist"], _map_from_json(al["valueMap"])),
+                            allowAlignment=True)
         kw = dict(zeroAsMissingData=meta["zeroAsMissingData"], fudge=float(z["fudge"]),
                   effectiveSegmentLength=None if eff < 0 else eff, randRange=tuple(meta["randRange"]))
         if meta["emission_class"] == "gaussian":
@@ -136,6 +183,19 @@ def loadModel(path):
         em.uniformMixProb = float(meta["uniformMixProb"])
         em.logProbs = lp.copy()
         em.normalizeFac = float(z["normalize_fac"])
+        if kind == KIND_CFG:
+            from .cfg import MultitrackCfg
+            from .emission import PairEmissionModel
+            pairEM = PairEmissionModel(em, [None] * lp.shape[1])
+            pairEM.logPriors = z["log_priors"].copy()
+            cfg = MultitrackCfg(em, pairEM, [int(x) for x in z["nest_states"]],
+                                state_name_map=_map_from_json(meta["stateNameMap"]))
+            cfg.logProbs1, cfg.logProbs2 = z["log_probs1"].copy(), z["log_probs2"].copy()
+            cfg.startProbs = z["log_startprob"].copy()
+            cfg.trackList = tl
+            cfg.createHelperTables()
+            cfg.validate()
+            return cfg
         h = meta["hmm"]
         hmm = MultitrackHmm(em, algorithm=h["algorithm"], n_iter=h["n_iter"], thresh=h["thresh"],
                             state_name_map=_map_from_json(meta["stateNameMap"]), fudge=h["fudge"],

@@ -499,12 +499,27 @@ class TrackList(list):
                 return t
         return None
 
-    def addTrack(self, track, treatMaskAsBinary=False):
-        """track.py:280-294: the track's number becomes its position in its list"""
-        if track.getDist() == "alignment":
-            raise NotImplementedError("track %s: alignment tracks belong to the SCFG, which is not offered"
-                                      % track.getName())
+    def getAlignmentTrack(self):
+        """The one alignment track (track.py:277-278), kept apart from the tracks a model emits; None without one."""
+        return self.__dict__.get("alignmentTrack")
+
+    def addTrack(self, track, treatMaskAsBinary=False, allowAlignment=False):
+        """track.py:280-294: the track's number becomes its position in its list.  An alignment track is read by the
+        grammar model alone: only a caller that says so (allowAlignment) gets one, at most one, number 0."""
         names = [t.getName() for t in self] + [t.getName() for t in self.getMaskTracks()]
+        if self.getAlignmentTrack() is not None:
+            names.append(self.getAlignmentTrack().getName())
+        if track.getDist() == "alignment":
+            if not allowAlignment:
+                raise NotImplementedError("track %s: alignment tracks belong to the grammar model (--cfg); no other "
+                                          "path reads them" % track.getName())
+            if self.getAlignmentTrack() is not None:
+                raise RuntimeError("Only one track with alignment distribution permitted")
+            if track.getName() in names:
+                raise ValueError("track name %s appears twice" % track.getName())
+            track.number = 0
+            self.__dict__["alignmentTrack"] = track
+            return
         if track.getName() in names:
             raise ValueError("track name %s appears twice" % track.getName())
         target = self.getMaskTracks() if track.getDist() == "mask" and not treatMaskAsBinary else self
@@ -517,15 +532,17 @@ class TrackList(list):
         root = ET.Element("teModelConfig")
         for track in list(self) + self.getMaskTracks():
             root.append(track.toXMLElement())
+        if self.getAlignmentTrack() is not None:
+            root.append(self.getAlignmentTrack().toXMLElement())
         with open(path, "w") as f:
             f.write(xml.dom.minidom.parseString(ET.tostring(root)).toprettyxml())
 
 
-def readTrackList(xmlPath, treatMaskAsBinary=False):
+def readTrackList(xmlPath, treatMaskAsBinary=False, allowAlignment=False):
     """The TrackList of an XML track list: the <track> elements below its root (track.py:308-320)."""
     tracks = TrackList()
     for child in ET.parse(xmlPath).getroot().findall("track"):
-        tracks.addTrack(Track.fromXMLElement(child), treatMaskAsBinary)
+        tracks.addTrack(Track.fromXMLElement(child), treatMaskAsBinary, allowAlignment)
     return tracks
 
 
@@ -536,9 +553,14 @@ class TrackData(object):
         self.trackTableList = list(trackTableList) if trackTableList is not None else []
         self.trackList = trackList
         self.numSymbolsPerTrack = numSymbolsPerTrack
+        self.alignmentTrackTableList = []
 
     def getTrackTableList(self):
         return self.trackTableList
+
+    def getAlignmentTrackTableList(self):
+        """One 1-row uint16 table per interval when the track list holds an alignment track, else empty."""
+        return self.alignmentTrackTableList
 
     def getTrackList(self):
         return self.trackList
@@ -556,7 +578,7 @@ class TrackData(object):
         return self.numSymbolsPerTrack
 
     def loadTrackData(self, trackListPath, intervals, trackList=None, segmentIntervals=None, interpolateSegments=True,
-                      applyMasking=True, treatMaskAsBinary=False):
+                      applyMasking=True, treatMaskAsBinary=False, allowAlignment=False):
         """track.py:874-955: the tables of the intervals (chrom, start, end, ...) from the files of an XML track list.
         trackList None: the list is the XML's and its value maps learn the values, in (interval, track) order; else the
         given (learned) list maps them, unseen values go to the missing value, and tracks it does not know are skipped
@@ -566,11 +588,12 @@ class TrackData(object):
         done table by table, so that its map sees the values in the reference's order."""
         from . import trackIO
         assert len(intervals) > 0
-        inputList = readTrackList(trackListPath, treatMaskAsBinary)
+        inputList = readTrackList(trackListPath, treatMaskAsBinary, allowAlignment)
         init = trackList is None
         self.trackList = inputList if init else trackList
         self.numSymbolsPerTrack = None
         self.trackTableList = []
+        self.alignmentTrackTableList = []
         numTracks = len(self.trackList)
         if numTracks < 1 or numTracks > trackIO.MAX_TRACKS:
             raise ValueError("%d tracks: a table holds 1 to %d" % (numTracks, trackIO.MAX_TRACKS))
@@ -620,3 +643,17 @@ class TrackData(object):
                 if segmentIntervals is not None:
                     table.segment(segmentIntervals, self.trackList, interpolate=interpolateSegments)
                 self.trackTableList.append(table)
+        # the alignment track (track.py:957-968): one uint16 row per interval, its own value map learning every value
+        # (the grammar model only compares its symbols with each other and with the default symbol 0)
+        inputTrack = inputList.getAlignmentTrack()
+        selfTrack = self.trackList.getAlignmentTrack()
+        if allowAlignment and inputTrack is not None and selfTrack is not None:
+            if segmentIntervals is not None or any(t.hasMask() for t in self.trackTableList):
+                raise RuntimeError("an alignment track cannot follow rows that a mask or segments have cut out")
+            for iv in intervals:
+                row = trackIO.readTrackData(inputTrack.getPath(), iv[0], int(iv[1]), int(iv[2]),
+                                            valCol=inputTrack.getValCol(), valMap=selfTrack.getValueMap(),
+                                            updateValMap=True)
+                table = IntegerTrackTable(1, iv[0], int(iv[1]), int(iv[2]), dtype=np.uint16)
+                table.writeRow(0, row)
+                self.alignmentTrackTableList.append(table)

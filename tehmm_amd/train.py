@@ -1,7 +1,8 @@
-"""teHmmTrain -- the reference's bin/teHmmTrain.py (without --cfg, whose grammar model is not offered): build a
-MultitrackHmm from track files and train it supervised (state names of the training BED), by Baum-Welch, or
-semi-supervised -- Baum-Welch from user start / transition / emission files (--init*Probs), with entries pinned through
-every iteration (--force*Probs).
+"""teHmmTrain -- the reference's bin/teHmmTrain.py: build a MultitrackHmm from track files and train it supervised
+(state names of the training BED), by Baum-Welch, or semi-supervised -- Baum-Welch from user start / transition /
+emission files (--init*Probs), with entries pinned through every iteration (--force*Probs); or, with --cfg
+--supervised, a MultitrackCfg whose --pairStates emit pairs of columns under the --saPrior confidence in the track
+list's alignment track.
 
 Same options, the same conflicts between them and the same default for transMatEpsilons as the reference
 (teHmmTrain.py:188-225).  Tracks are loaded through TrackData.loadTrackData, the model is written by modelIO.  Where
@@ -33,12 +34,13 @@ def parseArgs(argv):
                         "the model.  Transition parameters will be estimated directly from this information rather "
                         "than EM.  NOTE: The number of states will be determined from the bed.",
                         action="store_true", default=False)
-    parser.add_argument("--cfg", help="Context free grammar instead of HMM: not offered by this package",
+    parser.add_argument("--cfg", help="Use Context Free Grammar instead of HMM.  Only works with --supervised",
                         action="store_true", default=False)
-    parser.add_argument("--saPrior", help="Confidence in self alignment track for CFG (only with --cfg)", default=0.95,
-                        type=float)
-    parser.add_argument("--pairStates", help="Comma-separated list of pair-emitting states for the CFG (only with "
-                        "--cfg)", default=None)
+    parser.add_argument("--saPrior", help="Confidence in self alignment track for CFG.  Probability of pair emission "
+                        "is multiplied by this number if the bases are aligned and its complement if bases are not "
+                        "aligned. Must be between [0,1].", default=0.95, type=float)
+    parser.add_argument("--pairStates", help="Comma-separated list of states (from trainingBed) that are treated as "
+                        "pair-emitors for the CFG", default=None)
     parser.add_argument("--emFac", help="Normalization factor for weighting emission probabilities because when "
                         "there are many tracks, the transition probabilities can get totally lost. 0 = no "
                         "normalization. 1 = divide by number of tracks.  k = divide by number of tracks / k",
@@ -113,8 +115,18 @@ def parseArgs(argv):
 def checkArgs(args):
     """The conflicts teHmmTrain.py:188-225 raises on, and its default for transMatEpsilons."""
     if args.cfg is True:
-        raise RuntimeError("--cfg: the context free grammar model is not offered by this package")
-    assert args.pairStates is None, "--pairStates needs --cfg"
+        if args.supervised is not True:
+            raise RuntimeError("--cfg only works with --supervised")
+        if not 0. <= args.saPrior <= 1.:
+            raise RuntimeError("--saPrior must be between [0,1]")
+        if (args.initTransProbs is not None or args.fixTrans is True or args.initEmProbs is not None or
+                args.fixEm is True or args.initStartProbs is not None):
+            raise RuntimeError("--initTransProbs, --fixTrans, --initEmProbs, --fixEm, --initStartProbs are not "
+                               "compatible with --cfg.")
+        if args.forceTransProbs is not None or args.forceEmProbs is not None:
+            raise RuntimeError("--forceTransProbs and --forceEmProbs are not compatible with --cfg")
+    elif args.pairStates is not None:
+        raise RuntimeError("--pairStates needs --cfg")
     if args.fixTrans is True and args.supervised is True:
         raise RuntimeError("--fixTrans option not compatible with --supervised")
     if args.fixEm is True and args.supervised is True:
@@ -166,7 +178,7 @@ def main(argv=None):
 
     logger.info("loading tracks %s" % args.tracksInfo)
     trackData = TrackData()
-    trackData.loadTrackData(args.tracksInfo, mergedIntervals, segmentIntervals=segIntervals)
+    trackData.loadTrackData(args.tracksInfo, mergedIntervals, segmentIntervals=segIntervals, allowAlignment=args.cfg)
 
     catMap = None
     if args.supervised is False and args.initTransProbs is not None:
@@ -220,6 +232,21 @@ def trainModel(randomSeed, trackData, catMap, userTrans, truthIntervals, args):
     emissionModel = IndependentMultinomialAndGaussianEmissionModel(
         args.numStates, trackData.getNumSymbolsPerTrack(), trackData.getTrackList(), normalizeFac=args.emFac,
         randomize=randomize, effectiveSegmentLength=args.segLen, random_state=randGen, randRange=args.emRandRange)
+    if args.cfg is True:
+        # teHmmTrain.py:364-374
+        from .cfg import MultitrackCfg
+        from .emission import PairEmissionModel
+        pairEM = PairEmissionModel(emissionModel, [args.saPrior] * emissionModel.getNumStates())
+        nestStates = []
+        if args.pairStates is not None:
+            for name in args.pairStates.split(","):
+                if not catMap.has(name):
+                    raise RuntimeError("--pairStates: state %s is not in the training BED" % name)
+                nestStates.append(catMap.getMap(name))
+        logger.info("Creating cfg model")
+        model = MultitrackCfg(emissionModel, pairEM, nestStates, state_name_map=catMap)
+        model.supervisedTrain(trackData, truthIntervals)
+        return model
     model = MultitrackHmm(emissionModel, n_iter=args.iter, state_name_map=catMap, fixTrans=args.fixTrans,
                           fixEmission=args.fixEm, fixStart=args.fixStart, forceUserEmissions=args.forceEmProbs,
                           forceUserTrans=args.forceTransProbs, random_state=randGen, thresh=args.emThresh,
