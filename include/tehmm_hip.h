@@ -584,6 +584,48 @@ int tehmm_cyk_last_timing(int max_entries, const char **names, double *milliseco
 /* Bytes of device memory a decode of intervals of these lengths takes (no device call). */
 int64_t tehmm_cyk_workspace_bytes(int n_intervals, const int64_t *lengths, int M);
 
+/* ---- BED text parsed on the device (trackIO.bedRead and what BedFile builds from it) -------------------
+ * tehmm_bed_parse_open takes the bytes of one file (host memory; a tehmm_host_alloc block makes the upload one DMA) and
+ * parses them by bedRead's rule: lines end at "\n", "\r\n" or a lone "\r", a last line without a terminator counts, a
+ * line whose first byte is '#' or that has fewer than three tab-separated fields is dropped.  The handle keeps the text
+ * and the tables on the device until tehmm_bed_parse_close.  All results are in file order over the KEPT records.
+ * TEHMM_ERR_UNSUPPORTED (nothing parsed; the caller's host route serves the file) when text plus columns exceed the
+ * workspace budget -- seven eighths of the free device memory, pooled blocks counted as free, or
+ * TEHMM_BED_PARSE_MAX_WORKSPACE bytes if that is less -- or when a record has 2^31 bytes or more.  A file with a byte
+ * >= 0x80 is not parsed either: tehmm_bed_parse_counts reports high_bytes > 0 and the getters return TEHMM_ERR_ARG.
+ * Additions to ABI version 4: detect them by symbol. */
+typedef struct tehmm_bedparse tehmm_bedparse_t;
+int tehmm_bed_parse_open(const void *text, int64_t n_bytes, tehmm_bedparse_t **out);
+int tehmm_bed_parse_close(tehmm_bedparse_t *h);
+int tehmm_bed_parse_counts(tehmm_bedparse_t *h, int64_t *lines, int64_t *records, int64_t *high_bytes);
+/* line_start / line_len [records]: the record's bytes without its terminator; n_fields [records]; field_off / field_len
+ * [records][6]: columns 0..5, offsets from the record's first byte, length -1 where the record has no such column. */
+int tehmm_bed_parse_get_table(tehmm_bedparse_t *h, int64_t *line_start, int64_t *line_len, int32_t *n_fields,
+                              int32_t *field_off, int32_t *field_len);
+/* Column col (0..5) as numbers: kind 0 integers into ivalue, kind 1 floats into fvalue; status [records]: 0 certified
+ * (the value equals Python's int() / float() of the field), 1 left to the host's int() / float(), 2 no such column.
+ * Certified: integers [+-]?[0-9]{1,18}; floats [+-]? digits with at most one '.' and an optional [eE][+-]?digits, at
+ * most 15 significant digits (first non-zero digit to the last digit) and |exponent - fraction digits| <= 22, or a
+ * mantissa of zeros. */
+int tehmm_bed_parse_get_numbers(tehmm_bedparse_t *h, int col, int kind, int64_t *ivalue, double *fvalue, uint8_t *status);
+/* Column col (0..5) as codes: codes [records] numbers the distinct byte strings in order of first appearance (-1: no
+ * such column), first_records [records] gets, for each of the *n_distinct values, the record it first appears in.
+ * *n_missing / *n_empty count records without the column / with an empty value.  Values are found through a 64-bit hash
+ * (TEHMM_BED_PARSE_HASH_BITS in the environment at open truncates it: tests) and every record is then compared byte
+ * for byte with its value's first record; on any difference *fell_back = 1 and codes are not written. */
+int tehmm_bed_parse_get_codes(tehmm_bedparse_t *h, int col, int64_t *codes, int64_t *first_records, int64_t *n_distinct,
+                              int64_t *n_missing, int64_t *n_empty, int *fell_back);
+/* The number routines of the kernels run on the CPU (the same code; no GPU needed): kind and *status as above. */
+int tehmm_bed_parse_number(const char *text, int64_t len, int kind, int64_t *ivalue, double *fvalue, int *status);
+/* Bytes of text one workgroup classifies (tests place line ends across this boundary). */
+int64_t tehmm_bed_parse_tile_bytes(void);
+/* Since the calling thread's last open: lines, kept records, integer and float fields left to the host, code columns
+ * that fell back; and the device passes ("upload", "classify", "scan_tiles", "lines", "keep", "scan_lines", "fields",
+ * then "ints" / "floats" / "hash", "verify", "codes" per getter), as tehmm_segment_last_timing. */
+int tehmm_bed_parse_last_counters(int64_t *lines, int64_t *records, int64_t *host_ints, int64_t *host_floats,
+                                  int64_t *code_fallbacks);
+int tehmm_bed_parse_last_timing(int max_entries, const char **names, double *milliseconds);
+
 /* Forward log-likelihood of every interval from the last tehmm_estep_batch or posterior evaluation
  * (the per-sequence `lpr` of basehmm.py:513, which MultitrackHmm's best-iteration bookkeeping,
  * hmm.py:690-711, consumes sequence by sequence); out [n_intervals] host. */

@@ -110,6 +110,16 @@ SIGNATURES = {
     "tehmm_bed_text_format_value": (c_int, [c_dbl, ctypes.c_char_p, ctypes.POINTER(c_int)]),
     "tehmm_bed_text_last_counters": (c_int, [i64p, i64p, i64p]),
     "tehmm_bed_text_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
+    "tehmm_bed_parse_open": (c_int, [vp, c_i64, ctypes.POINTER(vp)]),
+    "tehmm_bed_parse_close": (c_int, [vp]),
+    "tehmm_bed_parse_counts": (c_int, [vp, i64p, i64p, i64p]),
+    "tehmm_bed_parse_get_table": (c_int, [vp, i64p, i64p, i32p, i32p, i32p]),
+    "tehmm_bed_parse_get_numbers": (c_int, [vp, c_int, c_int, i64p, f64p, u8p]),
+    "tehmm_bed_parse_get_codes": (c_int, [vp, c_int, i64p, i64p, i64p, i64p, i64p, ctypes.POINTER(c_int)]),
+    "tehmm_bed_parse_number": (c_int, [ctypes.c_char_p, c_i64, c_int, i64p, f64p, ctypes.POINTER(c_int)]),
+    "tehmm_bed_parse_tile_bytes": (c_i64, []),
+    "tehmm_bed_parse_last_counters": (c_int, [i64p, i64p, i64p, i64p, i64p]),
+    "tehmm_bed_parse_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),
     "tehmm_cyk_decode": (c_int, [c_int, i64p, c_int, f64p, u16p, c_int, u8p, f64p, f64p, f64p, f64p, f64p, i64p, f64p]),
     "tehmm_cyk_get_dp": (c_int, [c_i64, c_int, f64p, u16p, c_int, u8p, f64p, f64p, f64p, f64p, f64p]),
     "tehmm_cyk_last_timing": (c_int, [c_int, ctypes.POINTER(ctypes.c_char_p), f64p]),

@@ -22,6 +22,7 @@
 #include "tehmm_scaling.hip.h"
 #include "tehmm_bedtext.hip.h"
 #include "tehmm_cyk.hip.h"
+#include "tehmm_bedparse.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -30,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -4200,6 +4202,7 @@ int tehmm_viterbi(int64_t T, int N, const double *pi, const double *lt, const do
 #include "tehmm_scaling_host.inc"
 #include "tehmm_bedtext_host.inc"
 #include "tehmm_cyk_host.inc"
+#include "tehmm_bedparse_host.inc"
 
 // Diagnostic: cycle stamps of the last cooperative kernel (only in the -DTEHMM_STAMPS build).
 int tehmm_debug_read_stamps(unsigned long long *out, int n) {

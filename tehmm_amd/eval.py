@@ -148,7 +148,7 @@ def runEval(args, out=None):
     segIntervals = None
     if args.segment is True:
         logger.info("loading segment intervals from %s" % args.bedRegions)
-        segIntervals = trackIO.readBedIntervals(args.bedRegions, sort=True)
+        segIntervals = trackIO.readBedColumns(args.bedRegions, sort=True)
 
     logger.info("loading tracks %s" % args.tracksInfo)
     trackData = TrackData()

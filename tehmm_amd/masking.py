@@ -213,8 +213,16 @@ def _track_list(trackList):
 
 
 def _mask_records(trackList):
-    from .trackIO import bedRead
-    return [(r[0], int(r[1]), int(r[2])) for t in trackList.getMaskTracks() for r in bedRead(t.getPath())]
+    return [iv for t in trackList.getMaskTracks() for iv in _bed_tuples(t.getPath(), 3)]
+
+
+def _bed_tuples(path, ncol):
+    """(chrom, int start, int end) + the text of columns 3 .. ncol - 1 (None: all) of the records of a BED file"""
+    from .trackIO import parseBed
+    cols = parseBed(path)
+    if cols.intsCertified():
+        return cols.tuples(ncol)
+    return [(r[0], int(r[1]), int(r[2])) + tuple(r[3:ncol]) for r in cols.fields]
 
 
 def maskIntervals(trackList):
@@ -224,8 +232,7 @@ def maskIntervals(trackList):
 
 def readBed(path):
     """the records of a BED file as tuples (chrom, int start, int end, other fields as text ...)"""
-    from .trackIO import bedRead
-    return [(r[0], int(r[1]), int(r[2])) + tuple(r[3:]) for r in bedRead(path)]
+    return _bed_tuples(path, None)
 
 
 def writeBed(intervals, path):

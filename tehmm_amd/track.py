@@ -95,9 +95,16 @@ class TrackTable(object):
         from . import _lib
         from ._lib import f64p, i64p, ptr, u8p
         first_end = self.origEnd if self.maskArray is not None else self.end
-        ivs = [iv for iv in segIntervals if iv[0] == self.chrom and iv[1] >= self.start and iv[2] <= first_end]
-        assert ivs and ivs[0][1] == self.start and ivs[-1][2] == first_end
-        offs = np.asarray([int(iv[1]) - self.start for iv in ivs], dtype=np.int64)
+        if hasattr(segIntervals, "intervals"):          # BedColumns: its intervals in file order
+            segIntervals = segIntervals.intervals(sort=False)
+        if hasattr(segIntervals, "window"):             # IntervalColumns: binary searches instead of the scan
+            segStart, segEnd = segIntervals.window(self.chrom, self.start, first_end)
+            assert len(segStart) and segStart[0] == self.start and segEnd[-1] == first_end
+            offs = (segStart - self.start).astype(np.int64)
+        else:
+            ivs = [iv for iv in segIntervals if iv[0] == self.chrom and iv[1] >= self.start and iv[2] <= first_end]
+            assert ivs and ivs[0][1] == self.start and ivs[-1][2] == first_end
+            offs = np.asarray([int(iv[1]) - self.start for iv in ivs], dtype=np.int64)
         if self.maskArray is not None:
             run = self.getMaskRunningOffsets(reverseTransform=True)
             kept = self.maskArray[offs]                 # a segment is either all kept or all cut

@@ -27,8 +27,15 @@ Without a value map and with a float32 outputBuf (what bin/setTrackScaling.py of
 5p) a BED record's value is np.float32(float(text)), or 1 for valCol 0, and the rows no record covers keep what the
 buffer held.  Text that is no number raises ValueError as in the reference; a value that is not finite raises
 ValueError naming the track (deliberate).  useDelta=True is not offered there.
+
+BED text itself is read by parseBed into BedColumns: by bedRead and the interpreter (the host
+route, the specification) or, for files of 1 MiB and more when there is a device, by the kernels of
+tehmm_bedparse.hip.h, which certify what they return and leave the rest to the host's int() / float() / dict.  BedFile,
+readBedIntervals and the loaders stand on the columns and return the same either way.
 """
 import ctypes
+import logging
+import operator
 import os
 import sys
 
@@ -36,6 +43,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import f32p, i64p, ptr, u8p
+
+logger = logging.getLogger(__name__)
 
 MAX_SYMBOL = 255
 MAX_TRACKS = 128
@@ -55,6 +64,436 @@ def bedRead(path):
     return out
 
 
+# ---- BED columns ------------------------------------------------------------------------------------------------------
+# The records of a file as columns.  Two routes build them: the host route is bedRead and the
+# interpreter's int() / dict, i.e. the specification; the device route parses the file's bytes with the kernels of
+# tehmm_bedparse.hip.h and leaves to the host's int() / float() / dict exactly what the device does not certify.
+BED_PARSE_MIN_BYTES = 1 << 20       # launch and copy overhead arithmetic, not a measurement
+PARSE_INT, PARSE_FLOAT = 0, 1
+CERTIFIED, LEFT_TO_HOST, NO_COLUMN = 0, 1, 2
+DEVICE_COLS = 6
+
+
+class _HostRoute(Exception):
+    """the device route hands the file to the host route (the reason is logged)"""
+
+
+class _FieldsView(object):
+    """fields[i] of a BedColumns without a list of lists: the text fields of record i, as bedRead returns them"""
+
+    def __init__(self, cols):
+        self.cols = cols
+
+    def __len__(self):
+        return self.cols.n
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(self.cols.n))]
+        i = operator.index(i)
+        if i < 0:
+            i += self.cols.n
+        if not 0 <= i < self.cols.n:
+            raise IndexError("list index out of range")
+        return self.cols.line(i).split("\t")
+
+    def __iter__(self):
+        for i in range(self.cols.n):
+            yield self[i]
+
+
+class BedColumns(object):
+    """The kept records of a BED file, in file order, as columns.  route: "host" or "device"; n: records; numFields
+    (int32); start / end (int64: int() of columns 1 and 2); chromCode / chromNames; fields (a sequence of field lists);
+    raw (the file's bytes as uint8)."""
+    route = None
+
+    def __init__(self, path):
+        self.path = path
+        self._ints, self._floats, self._codes, self._chroms, self._intervals = dict(), dict(), dict(), None, dict()
+
+    # -- numbers ------------------------------------------------------------------------------------------------------
+    def ints(self, col):
+        """int() of every record's column col (int64); the first text that is no integer raises as int() does"""
+        if col not in self._ints:
+            self._ints[col] = self._int_column(col)
+        return self._ints[col]
+
+    @property
+    def start(self):
+        return self.ints(1)
+
+    @property
+    def end(self):
+        self.ints(1)                                  # (starts first: the order in which a bad number is met)
+        return self.ints(2)
+
+    def floats(self, col):
+        """(float64 values, bool: certified equal to float(text)) of column col; the rest is the caller's float()"""
+        if col not in self._floats:
+            self._floats[col] = self._float_column(col)
+        return self._floats[col]
+
+    def intsCertified(self):
+        """True: the device certified every start and end (the vectorised consumers need no int() of their own)"""
+        return False
+
+    # -- codes --------------------------------------------------------------------------------------------------------
+    def codes(self, col):
+        """(code per record, distinct raw values in order of first appearance) of a text column, as BedFile.codes"""
+        return self._strict_codes(col)[:2]
+
+    def codeFirst(self, col):
+        """the record in which each distinct value of codes(col) first appears"""
+        return self._strict_codes(col)[2]
+
+    def _strict_codes(self, col):
+        if col not in self._codes:
+            code, values, first, missing, empty = self._code_column(col)
+            if missing:
+                raise ValueError("%s: a record has no column %d" % (self.path, col))
+            if empty:
+                raise ValueError("%s: an empty value in column %d" % (self.path, col))
+            self._codes[col] = (code, values, first)
+        return self._codes[col]
+
+    def _chrom_codes(self):
+        if self._chroms is None:
+            code, values, _, _, _ = self._code_column(0)
+            self._chroms = (code, values)
+        return self._chroms
+
+    @property
+    def chromCode(self):
+        return self._chrom_codes()[0]
+
+    @property
+    def chromNames(self):
+        return self._chrom_codes()[1]
+
+    def _dict_codes(self, col):
+        """the host dictionary over the field texts: (code, values, first records, missing, empty)"""
+        table, first = dict(), []
+
+        def walk():
+            for i in range(self.n):
+                v = self.field(i, col)
+                c = table.get(v)
+                if c is None:
+                    c = table[v] = len(table)
+                    first.append(i)
+                yield c
+        try:
+            code = np.fromiter(walk(), dtype=np.int64, count=self.n)
+        except IndexError:
+            return None, None, None, 1, 0
+        return code, list(table), np.asarray(first, dtype=np.int64), 0, int("" in table)
+
+    # -- tuples -------------------------------------------------------------------------------------------------------
+    def tuples(self, ncol=None, order=None):
+        """[(chrom, int start, int end) + the text of columns 3 .. ncol - 1 (None: all)] of the records, or of the
+        records `order` in that order"""
+        s, e = self.start, self.end
+        idx = np.arange(self.n, dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64)
+        names = self.chromNames
+        chrom = [names[c] for c in self.chromCode[idx].tolist()]
+        if ncol == 3:
+            return list(zip(chrom, s[idx].tolist(), e[idx].tolist()))
+        fields = self.fields
+        return [(c, a, b) + tuple(fields[i][3:ncol]) for c, a, b, i in
+                zip(chrom, s[idx].tolist(), e[idx].tolist(), idx.tolist())]
+
+    def intervals(self, sort=False):
+        """IntervalColumns of the records (TrackTable.segment takes them)"""
+        if sort not in self._intervals:
+            self._intervals[sort] = IntervalColumns(self.chromNames, self.chromCode, self.start, self.end, sort=sort)
+        return self._intervals[sort]
+
+    def close(self):
+        pass
+
+
+class _HostBedColumns(BedColumns):
+    """bedRead and the interpreter: the specification"""
+    route = "host"
+
+    def __init__(self, path):
+        super(_HostBedColumns, self).__init__(path)
+        self.fields = bedRead(path)
+        self.n = len(self.fields)
+        self.numFields = np.fromiter((len(r) for r in self.fields), dtype=np.int32, count=self.n)
+        self._raw = None
+
+    @property
+    def raw(self):
+        if self._raw is None:
+            self._raw = np.fromfile(self.path, dtype=np.uint8)
+        return self._raw
+
+    def line(self, i):
+        return "\t".join(self.fields[i])
+
+    def field(self, i, col):
+        return self.fields[i][col]
+
+    def _int_column(self, col):
+        return np.fromiter((int(r[col]) for r in self.fields), dtype=np.int64, count=self.n)
+
+    def _float_column(self, col):
+        return np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=bool)
+
+    def _code_column(self, col):
+        return self._dict_codes(col)
+
+
+class _DeviceBedColumns(BedColumns):
+    """the parse of tehmm_bed_parse_open; the handle keeps text and tables on the device for later columns"""
+    route = "device"
+
+    def __init__(self, path):
+        super(_DeviceBedColumns, self).__init__(path)
+        lib = _lib.load()
+        self._handle = None
+        self.raw = _read_pinned(path)
+        h = _lib.vp()
+        rc = lib.tehmm_bed_parse_open(_lib.vp(self.raw.ctypes.data), len(self.raw), ctypes.byref(h))
+        if rc == -3:
+            raise _HostRoute(lib.tehmm_last_error().decode())
+        _lib.check(rc, "tehmm_bed_parse_open")
+        self._handle = h
+        lines, n, high = _lib.c_i64(0), _lib.c_i64(0), _lib.c_i64(0)
+        _lib.check(lib.tehmm_bed_parse_counts(h, ctypes.byref(lines), ctypes.byref(n), ctypes.byref(high)),
+                   "tehmm_bed_parse_counts")
+        if high.value > 0:
+            self.close()
+            raise _HostRoute("bytes >= 0x80: decoding them is the locale's business")
+        self.n, self.numLines = int(n.value), int(lines.value)
+        self.lineStart, self.lineLen = np.empty(self.n, dtype=np.int64), np.empty(self.n, dtype=np.int64)
+        self.numFields = np.empty(self.n, dtype=np.int32)
+        self.fieldOff = np.empty((self.n, DEVICE_COLS), dtype=np.int32)
+        self.fieldLen = np.empty((self.n, DEVICE_COLS), dtype=np.int32)
+        _lib.check(lib.tehmm_bed_parse_get_table(h, ptr(self.lineStart, i64p), ptr(self.lineLen, i64p),
+                                                 ptr(self.numFields, _lib.i32p), ptr(self.fieldOff, _lib.i32p),
+                                                 ptr(self.fieldLen, _lib.i32p)), "tehmm_bed_parse_get_table")
+        self.fields = _FieldsView(self)
+        self._text = None
+        self._status = dict()
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            _lib.load().tehmm_bed_parse_close(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def text(self):
+        """the file as one str (no byte is >= 0x80: offsets are the bytes'), decoded when text is first asked for"""
+        if self._text is None:
+            self._text = self.raw.tobytes().decode("ascii")
+        return self._text
+
+    def line(self, i):
+        a = int(self.lineStart[i])
+        return self.text()[a:a + int(self.lineLen[i])]
+
+    def field(self, i, col):
+        if col >= DEVICE_COLS:
+            return self.fields[i][col]
+        n = int(self.fieldLen[i, col])
+        if n < 0:
+            raise IndexError("list index out of range")
+        a = int(self.lineStart[i]) + int(self.fieldOff[i, col])
+        return self.text()[a:a + n]
+
+    def numbers(self, col, kind):
+        """(values, status bytes) of the device's routine over column col (0 .. 5), nothing added by the host"""
+        val = np.zeros(self.n, dtype=np.int64 if kind == PARSE_INT else np.float64)
+        status = np.zeros(self.n, dtype=np.uint8)
+        _lib.check(_lib.load().tehmm_bed_parse_get_numbers(
+            self._handle, col, kind, ptr(val, i64p) if kind == PARSE_INT else None,
+            ptr(val, _lib.f64p) if kind == PARSE_FLOAT else None, ptr(status, u8p)), "tehmm_bed_parse_get_numbers")
+        return val, status
+
+    def _int_column(self, col):
+        if col >= DEVICE_COLS:
+            return np.fromiter((int(r[col]) for r in self.fields), dtype=np.int64, count=self.n)
+        val, status = self._device_ints(col)
+        val = val.copy()
+        for i in np.flatnonzero(status != CERTIFIED).tolist():      # file order: the first error is bedRead's first
+            val[i] = int(self.field(i, col))
+        return val
+
+    def _device_ints(self, col):
+        if col not in self._status:
+            self._status[col] = self.numbers(col, PARSE_INT)
+        return self._status[col]
+
+    def _float_column(self, col):
+        if col >= DEVICE_COLS:
+            return np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=bool)
+        val, status = self.numbers(col, PARSE_FLOAT)
+        return val, status == CERTIFIED
+
+    def intsCertified(self):
+        return all(bool((self._device_ints(col)[1] == CERTIFIED).all()) for col in (1, 2))
+
+    def _code_column(self, col):
+        if col >= DEVICE_COLS:
+            return self._dict_codes(col)
+        code, first = np.zeros(self.n, dtype=np.int64), np.zeros(self.n, dtype=np.int64)
+        nd, missing, empty, fell = _lib.c_i64(0), _lib.c_i64(0), _lib.c_i64(0), _lib.c_int(0)
+        _lib.check(_lib.load().tehmm_bed_parse_get_codes(
+            self._handle, col, ptr(code, i64p), ptr(first, i64p), ctypes.byref(nd), ctypes.byref(missing),
+            ctypes.byref(empty), ctypes.byref(fell)), "tehmm_bed_parse_get_codes")
+        if missing.value:
+            return None, None, None, int(missing.value), int(empty.value)
+        if fell.value:                                # two values behind one hash: the host dictionary decides
+            logger.info("%s: column %d coded by the host dictionary (hash collision)" % (self.path, col))
+            return self._dict_codes(col)
+        first = first[:int(nd.value)].copy()
+        return code, [self.field(i, col) for i in first.tolist()], first, 0, int(empty.value)
+
+
+def _read_pinned(path):
+    """the bytes of a file in a tehmm_host_alloc block (the upload is one DMA)"""
+    size = os.path.getsize(path)
+    buf = _lib.pinned_empty(size, np.uint8)
+    got = 0
+    with open(path, "rb", buffering=0) as f:
+        view = memoryview(buf)
+        while got < size:
+            k = f.readinto(view[got:])
+            if not k:
+                break
+            got += k
+    return buf[:got]
+
+
+def parseBed(path):
+    """BedColumns of a BED file.  TEHMM_BED_PARSE=0: the host route; =1: the device route (an error without a device);
+    unset: the device route for files of at least TEHMM_BED_PARSE_MIN_BYTES bytes (default 1 MiB) when there is a
+    device.  A file with a byte >= 0x80, or one whose text and columns exceed the workspace budget, takes the host
+    route from the device route, with the reason logged."""
+    mode = os.environ.get("TEHMM_BED_PARSE", "")
+    if mode not in ("", "0", "1"):
+        raise ValueError("TEHMM_BED_PARSE is 0 or 1")
+    device = False
+    if mode == "1":
+        if _lib.device_count() < 1:
+            raise RuntimeError("TEHMM_BED_PARSE=1: the device route needs a device and there is none")
+        device = True
+    elif mode == "":
+        minBytes = int(os.environ.get("TEHMM_BED_PARSE_MIN_BYTES", BED_PARSE_MIN_BYTES))
+        device = os.path.getsize(path) >= minBytes and _lib.device_count() > 0
+    if device:
+        try:
+            return _DeviceBedColumns(path)
+        except _HostRoute as e:
+            logger.info("%s: parsed on the host (%s)" % (path, e))
+    return _HostBedColumns(path)
+
+
+def parseCounters():
+    """lines, records, host_ints, host_floats, code_fallbacks since this thread's last device parse was opened"""
+    v = [_lib.c_i64(0) for _ in range(5)]
+    _lib.check(_lib.load().tehmm_bed_parse_last_counters(*[ctypes.byref(x) for x in v]), "tehmm_bed_parse_last_counters")
+    return dict(zip(("lines", "records", "host_ints", "host_floats", "code_fallbacks"), (int(x.value) for x in v)))
+
+
+def parseTiming():
+    """[(pass, milliseconds)] of the device passes since this thread's last device parse was opened"""
+    names = (ctypes.c_char_p * 64)()
+    ms = (ctypes.c_double * 64)()
+    n = _lib.load().tehmm_bed_parse_last_timing(64, names, ms)
+    _lib.check(min(n, 0), "tehmm_bed_parse_last_timing")
+    return [(names[i].decode(), ms[i]) for i in range(n)]
+
+
+def parseNumber(text, kind):
+    """(value, status) of the device's number routine run on the CPU (tehmm_bed_parse_number); text: bytes"""
+    iv, fv, st = _lib.c_i64(0), _lib.c_dbl(0.0), _lib.c_int(0)
+    _lib.check(_lib.load().tehmm_bed_parse_number(text, len(text), kind, ctypes.byref(iv), ctypes.byref(fv),
+                                                  ctypes.byref(st)), "tehmm_bed_parse_number")
+    return (iv.value if kind == PARSE_INT else fv.value), st.value
+
+
+def parseTileBytes():
+    return int(_lib.load().tehmm_bed_parse_tile_bytes())
+
+
+class IntervalColumns(object):
+    """Intervals (chrom, start, end) as arrays, in list order, or with sort stably by (chrom name, start) as
+    readBedIntervals(sort=True) orders them; window() is what TrackTable.segment asks of its segment list."""
+
+    def __init__(self, chromNames, chromCode, start, end, sort=False):
+        code = np.asarray(chromCode, dtype=np.int64)
+        start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+        self.sorted = bool(sort)
+        self.chromNames = list(chromNames)
+        if sort:
+            rank = np.zeros(len(self.chromNames), dtype=np.int64)
+            rank[np.asarray(sorted(range(len(self.chromNames)), key=lambda c: self.chromNames[c]), dtype=np.int64)] = \
+                np.arange(len(self.chromNames))
+            order = np.lexsort((start, rank[code])) if len(code) else np.zeros(0, dtype=np.int64)
+            code, start, end = code[order], start[order], end[order]
+            self.order = order
+            byRank = rank[code]
+            self._slices = dict()
+            for c, name in enumerate(self.chromNames):
+                self._slices[name] = (int(np.searchsorted(byRank, rank[c], side="left")),
+                                      int(np.searchsorted(byRank, rank[c], side="right")))
+        else:
+            self.order = np.arange(len(code), dtype=np.int64)
+            self._index = {name: c for c, name in enumerate(self.chromNames)}
+        self.chromCode, self.start, self.end = code, start, end
+
+    @classmethod
+    def fromTuples(cls, intervals, sort=False):
+        table = dict()
+        code = np.fromiter((table.setdefault(iv[0], len(table)) for iv in intervals), dtype=np.int64,
+                           count=len(intervals))
+        start = np.fromiter((int(iv[1]) for iv in intervals), dtype=np.int64, count=len(intervals))
+        end = np.fromiter((int(iv[2]) for iv in intervals), dtype=np.int64, count=len(intervals))
+        return cls(list(table), code, start, end, sort=sort)
+
+    def __len__(self):
+        return len(self.start)
+
+    def tuples(self):
+        return list(zip([self.chromNames[c] for c in self.chromCode.tolist()], self.start.tolist(), self.end.tolist()))
+
+    def window(self, chrom, start, end):
+        """(starts, ends) of the intervals of chrom with start >= `start` and end <= `end`, in list order"""
+        if self.sorted:
+            if chrom not in self._slices:
+                z = np.zeros(0, dtype=np.int64)
+                return z, z
+            a, b = self._slices[chrom]
+            lo = a + int(np.searchsorted(self.start[a:b], start, side="left"))
+            hi = a + int(np.searchsorted(self.start[a:b], end, side="right"))   # (an interval inside ends by `end`)
+            s, e = self.start[lo:hi], self.end[lo:hi]
+            keep = e <= end
+        else:
+            c = self._index.get(chrom, -1)
+            keep = (self.chromCode == c) & (self.start >= start) & (self.end <= end)
+            s, e = self.start, self.end
+        return s[keep], e[keep]
+
+
+def readBedColumns(bedPath, sort=False):
+    """The intervals of readBedIntervals(bedPath, 3, sort=sort) as IntervalColumns"""
+    if not os.path.isfile(bedPath):
+        raise RuntimeError("Bed interval file %s not found" % bedPath)
+    cols = parseBed(bedPath)
+    if cols.intsCertified():
+        return cols.intervals(sort=sort)
+    return IntervalColumns.fromTuples(_bed_intervals(cols, bedPath, 3, None, None, None, sort))
+
+
 def _clip(records, chrom, start, end):
     """rule step 2 on tuples / lists whose first three fields are chrom, start, end: [(oStart, oEnd, record)]"""
     kept = [(max(start, int(r[1])), min(end, int(r[2])), r) for r in records
@@ -69,7 +508,30 @@ def readBedIntervals(bedPath, ncol=3, chrom=None, start=None, end=None, sort=Fal
     if not os.path.isfile(bedPath):
         raise RuntimeError("Bed interval file %s not found" % bedPath)
     assert ncol in (3, 4, 5)
-    recs = bedRead(bedPath)
+    cols = parseBed(bedPath)
+    if not cols.intsCertified():
+        return _bed_intervals(cols, bedPath, ncol, chrom, start, end, sort)
+    short = np.flatnonzero(cols.numFields < ncol)
+    if len(short):
+        raise ValueError("%s: a line has %d fields, ncol = %d" % (bedPath, int(cols.numFields[short[0]]), ncol))
+    order = cols.intervals(sort=True).order if sort else np.arange(cols.n, dtype=np.int64)
+    if chrom is None:
+        return cols.tuples(ncol, order)
+    assert start is not None and end is not None
+    start, end = int(start), int(end)
+    names = cols.chromNames
+    s, e = cols.start[order], cols.end[order]
+    keep = (cols.chromCode[order] == (names.index(chrom) if chrom in names else -1)) & (e > start) & (s < end) & (e > s)
+    order, oStart, oEnd = order[keep], np.maximum(start, s[keep]), np.minimum(end, e[keep])
+    by = np.argsort(oStart, kind="stable")
+    rows = cols.tuples(ncol, order[by])
+    return [(chrom, a, b) + r[3:] for a, b, r in zip(oStart[by].tolist(), oEnd[by].tolist(), rows)]
+
+
+def _bed_intervals(cols, bedPath, ncol, chrom, start, end, sort):
+    """readBedIntervals over field lists, record by record: the host route, and the device route's way for a file with
+    a start or end that the device did not certify (every int() then runs where and when it always did)"""
+    recs = cols.fields
     for r in recs:
         if len(r) < ncol:
             raise ValueError("%s: a line has %d fields, ncol = %d" % (bedPath, len(r), ncol))
@@ -106,21 +568,19 @@ class BedFile(object):
         if not os.path.isfile(path):
             raise RuntimeError("Track file not found %s\n" % path)
         self.path = path
-        self.fields = bedRead(path)
-        n = len(self.fields)
-        start = np.fromiter((int(r[1]) for r in self.fields), dtype=np.int64, count=n)
-        end = np.fromiter((int(r[2]) for r in self.fields), dtype=np.int64, count=n)
-        groups = dict()
-        for i, r in enumerate(self.fields):
-            groups.setdefault(r[0], []).append(i)
+        self.columns = parseBed(path)
+        self.fields = self.columns.fields
+        start, end = self.columns.start, self.columns.end
+        code, names = self.columns.chromCode, self.columns.chromNames
+        byCode = np.argsort(code, kind="stable")          # the records of each chromosome, in file order
+        cut = np.concatenate([[0], np.cumsum(np.bincount(code, minlength=len(names)))]).astype(np.int64)
         self.start, self.end = start, end
         self.chroms = dict()
-        for c, idx in groups.items():
-            idx = np.asarray(idx, dtype=np.int64)
+        for c, name in enumerate(names):
+            idx = byCode[cut[c]:cut[c + 1]].astype(np.int64)
             idx = idx[end[idx] > start[idx]]
             idx = idx[np.argsort(start[idx], kind="stable")]
-            self.chroms[c] = (idx, start[idx], np.maximum.accumulate(end[idx]) if len(idx) else end[idx])
-        self._codes = dict()
+            self.chroms[name] = (idx, start[idx], np.maximum.accumulate(end[idx]) if len(idx) else end[idx])
 
     def select(self, chrom, start, end):
         """(record index, oStart, oEnd) of rule step 2, as int64 arrays"""
@@ -139,17 +599,7 @@ class BedFile(object):
 
     def codes(self, col):
         """(code per record, distinct raw values) of a text column; a record without the column raises"""
-        if col not in self._codes:
-            table = dict()
-            try:
-                code = np.fromiter((table.setdefault(r[col], len(table)) for r in self.fields), dtype=np.int64,
-                                   count=len(self.fields))
-            except IndexError:
-                raise ValueError("%s: a record has no column %d" % (self.path, col))
-            if "" in table:
-                raise ValueError("%s: an empty value in column %d" % (self.path, col))
-            self._codes[col] = (code, list(table))
-        return self._codes[col]
+        return self.columns.codes(col)
 
 
 def _check_symbols(sym, name):
@@ -348,8 +798,11 @@ def recordValues(bed, pick, valCol, name):
         return np.ones(len(pick), dtype=np.float32)
     code, values = bed.codes(col)
     uniq, inv = np.unique(code[pick], return_inverse=True)
+    first = bed.columns.codeFirst(col)[uniq]          # a value's float is that of the record it first appears in
+    fval, certified = bed.columns.floats(col)
     with np.errstate(over="ignore"):
-        table = np.asarray([np.float32(float(values[int(u)])) for u in uniq], dtype=np.float32)
+        table = np.asarray([np.float32(fval[r] if certified[r] else float(values[int(u)]))
+                            for u, r in zip(uniq.tolist(), first.tolist())], dtype=np.float32)
     if not np.isfinite(table).all():
         raise ValueError("track %s: a value that is not finite (%s)" % (name, table[~np.isfinite(table)][0]))
     return table[inv.reshape(-1)]

@@ -170,7 +170,7 @@ def main(argv=None):
     segIntervals = None
     if args.segment is not None:
         logger.info("loading segment intervals from %s" % args.segment)
-        segIntervals = trackIO.readBedIntervals(args.segment, sort=True)
+        segIntervals = trackIO.readBedColumns(args.segment, sort=True)
         try:
             compare.checkExactOverlap(trackIO.readBedIntervals(args.trainingBed), trackIO.readBedIntervals(args.segment))
         except Exception:
